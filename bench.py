@@ -6,11 +6,14 @@ One step = the hot path over one file pair already resident in HBM:
   + Sender match scan over the source  (Sender.sendMatchesAndData, Sender.java:1235-1327)
 through the C-ABI (rsh_block_sums_device + rsh_match_scan_device).  Headline workload (BASELINE.json config 5):
 a 16 GiB source against an identical basis (every source block digested: the MD5-heavy case; --variant), B =
-131072, dl = 4, seed 01 02 03 04, splitmix64 synthetic bytes generated on the device; the 50%-modified basis and a
-1-byte shift run as companions under `variants`.  The serial whole-file MD5 runs on the host in the product
-(rsh_match_scan) and is excluded here (see DESIGN.md "Measurement").  The line also carries a `files` block:
-BASELINE config 4 (128 x 128 MiB per GPU, the job's 128*N-file list sharded over the N ranks) through the
-batched entry points.
+131072, dl = 4, seed 01 02 03 04, splitmix64 synthetic bytes generated on the device.  The serial whole-file MD5
+runs on the host in the product (rsh_match_scan) and is excluded here (see DESIGN.md "Measurement").
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line.
+`--full` adds everything else the line can carry: the 50%-modified basis and a 1-byte shift as companions under
+`variants`, a `files` block (BASELINE config 4: 128 x 128 MiB per GPU, the job's 128*N-file list sharded over the N
+ranks, through the batched entry points), the CPU baselines, the oracle check of the last step's events (`parity`),
+roofline.traffic and the clock the chip held under K1.  `--dump-outputs DIR` writes the last timed step's results.
 
 Multi-GPU: one process per GPU, each rank scans its own file pair (file-parallel sharding, no collective on the
 data path); value = all ranks' bytes / max-over-ranks time; the `files` block is config 4's 1024-file list at 8
@@ -66,7 +69,15 @@ def parse():
     ap.add_argument("--variant", choices=["identical", "half", "shift"], default="identical",
                     help="the headline pair (config 5): identical basis (every source block digested), 50%%-modified "
                          "basis, or an identical basis with one byte inserted into the source after 155 blocks")
-    ap.add_argument("--no-companions", action="store_true", help="skip the other two variants")
+    ap.add_argument("--full", action="store_true",
+                    help="the default workload: beside the headline, everything else the line reports -- the companion "
+                         "variants, the config-4 `files` block, the CPU baselines, the oracle parity check of the last "
+                         "step's events, roofline.traffic and the K1 clock (each can be dropped again with its --no-* "
+                         "option).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="the default workload: after the timed steps, write what the last timed step of the headline "
+                         "pair returned (block sums, match events, byte totals) as DIR/<name>.npy")
+    ap.add_argument("--no-companions", action="store_true", help="--full: skip the other two variants")
     ap.add_argument("--no-files", action="store_true",
                     help="--workload file: skip the config-4 `files` block (128 files per GPU, sharded list)")
     ap.add_argument("--workload", choices=["file", "files", "receiver"], default="file",
@@ -91,7 +102,10 @@ def parse():
                     help="library option for an A/B run (include/rsync_hip_debug.h; reported in the line)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rank plumbing only (gloo on CPU, no device): the line reports n_gpus and no value")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.dump_outputs and (a.workload != "file" or a.dry_run):
+        ap.error("--dump-outputs: the default workload (--workload file) on a device only")
+    return a
 
 
 def apply_opts(a):
@@ -209,7 +223,9 @@ def main():
     h = R.header_make(B, dl, n)
     R.header_validate(h)  # what the Sender's Connection.receiveChecksumHeader enforces
     C = h.chunk_count
-    golden = golden_cases(n, B, dl)
+    # a plain run does only what the headline needs; --full adds the rest (each piece has its --no-* option)
+    companions = a.full and not a.no_companions
+    golden = golden_cases(n, B, dl) if a.full else {}
 
     # ---- synthetic, device-resident inputs: the recipes of tests/fullsize_golden.py (config 5), so that the
     # timed scans can be checked against the oracle's committed digests of the same inputs afterwards.  Every
@@ -219,7 +235,7 @@ def main():
 
     src = torch.empty(n, dtype=torch.uint8, device="cuda")
     fill(src, KEY_CASE)
-    variants = [a.variant] + ([] if a.no_companions else [v for v in ("identical", "half", "shift") if v != a.variant])
+    variants = [a.variant] + ([v for v in ("identical", "half", "shift") if v != a.variant] if companions else [])
     pairs = {}
     for v in variants:
         if v == "identical":  # the basis is the source's bytes (the same buffer: 16 GiB each way is read)
@@ -337,13 +353,17 @@ def main():
                "speculation_kernel_ms": round(float(np.mean(spec_ms)), 4) if any(spec_ms) else None,
                "scan": {"events": int(n_ev.value), "literal": int(lit.value), "matched": int(mat.value),
                         "stats": st.as_dict()},
-               "parity": check_golden(golden.get(v), ev[:n_ev.value], lit.value, mat.value, B) if golden.get(v)
+               "parity": "unchecked (a plain run; --full checks the last step's events)" if not a.full
+               else check_golden(golden.get(v), ev[:n_ev.value], lit.value, mat.value, B) if golden.get(v)
                else check_identical(v, ev[:n_ev.value], lit.value, mat.value, ns, C)}
         return out, dt, gen_ms
 
     res_v = {}
     head, dt, gen_ms = run_variant(a.variant, a.steps, a.warmup)
     res_v[a.variant] = head
+    if a.dump_outputs and rank == 0:  # before a companion's steps overwrite the tables
+        dump_outputs(a.dump_outputs, d_weak[:C].cpu().numpy(), d_strong[:C * dl].cpu().numpy().reshape(C, dl),
+                     ev[:head["scan"]["events"]], head["scan"]["literal"], head["scan"]["matched"])
     for v in variants[1:]:
         res_v[v] = run_variant(v, max(2, min(a.steps, 3)), 1)[0]
 
@@ -393,7 +413,7 @@ def main():
             "frac": round(achieved / HBM_PEAK_GBS, 4),
             # the whole step (both K1s, the scan's host work and the gaps between them): bytes read / step / peak
             "step_frac": round(bytes_step / (head["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            "traffic": pmc_traffic(os.path.join(ROOT, "profiles", TRAFFIC_CSV), PROD_KERNEL, n),
+            "traffic": pmc_traffic(os.path.join(ROOT, "profiles", TRAFFIC_CSV), PROD_KERNEL, n) if a.full else None,
             "traffic_source": f"profiles/{TRAFFIC_CSV} (rocprofv3 --pmc FETCH_SIZE pass of this kernel, x2 gfx950 "
                               f"correction; a prior run, not this one)",
             "kernel_ms": round(gen_ms, 4),
@@ -408,15 +428,15 @@ def main():
     # s_memtime / s_memrealtime stamps, three launches over the resident source after the timed steps; the
     # production kernels never stamp (MI355X_MICROARCH.md, "DVFS give-back" item 6)
     ghz = ctypes.c_double(0.0)
-    if L.rsh_debug_k1_clock(ctx.handle, ctypes.c_void_p(src.data_ptr()), n, B, 3, ctypes.byref(ghz)) == 0:
+    if a.full and L.rsh_debug_k1_clock(ctx.handle, ctypes.c_void_p(src.data_ptr()), n, B, 3, ctypes.byref(ghz)) == 0:
         res["roofline"]["k1_clock_ghz"] = round(ghz.value, 3)
         res["roofline"]["k1_clock_source"] = ("3 launches of a stamped diagnostic instantiation of the Generator's K1 "
                                               "body over the same resident source, after the timed steps "
                                               "(rsh_debug_k1_clock; sum of s_memtime ticks / sum of 100 MHz ticks)")
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         b0, s0 = pairs[a.variant]
         res["cpu_baseline"] = cpu_baseline(s0, b0, B, dl, a.cpu_sample_mib << 20)
-    if not a.no_files and cfg_name(n, B) == "config5":
+    if a.full and not a.no_files and cfg_name(n, B) == "config5":
         # BASELINE config 4 beside the headline: this rank's shard of the job's 128*N-file list (1024 files at 8
         # GPUs), the same batched entry points and per-file oracle checks as --workload files
         del pairs, src, d_weak, d_strong
@@ -482,6 +502,29 @@ def check_golden(g, ev, lit, mat, B):
         G.events_sha(rec) == g["events_sha256"]
     assert ok, "the scan's match list differs from the oracle's digest of the same inputs"
     return f"events identical to the oracle (sha256 {g['events_sha256'][:16]}, {rec.size} events)"
+
+
+DUMP_MAX_BYTES = 60 * 10 ** 6  # --dump-outputs: the arrays of all files together (under 64 MB with the headers)
+
+
+def dump_outputs(path, weak, strong, ev, literal, matched):
+    """--dump-outputs DIR: what the headline pair's last timed step handed back, as float64 / float32 .npy files
+    (every value is an integer those formats hold exactly):
+      weak.npy    [C]      the Generator's rolling sums (rsh_block_sums_device)
+      strong.npy  [C, dl]  its truncated MD5 digests, one byte per element
+      events.npy  [E, 5]   the Sender's match list (rsh_match_scan_device): offset, length, kind, index, count
+      totals.npy  [3]      E, literal bytes, matched bytes
+    An array over its share of DUMP_MAX_BYTES is cut to a fixed, seeded sample of its rows (in order)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"weak": weak.astype(np.float64), "strong": strong.astype(np.float32),
+              "events": np.stack([ev[k].astype(np.float64) for k in ("offset", "length", "kind", "index", "count")], 1),
+              "totals": np.array([ev.size, literal, matched], np.float64)}
+    share = DUMP_MAX_BYTES // len(arrays)
+    for name, x in arrays.items():
+        if x.nbytes > share:
+            rows = max(1, share // (x.nbytes // x.shape[0]))
+            x = x[np.sort(np.random.default_rng(0x5EED).choice(x.shape[0], rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def main_files(a):

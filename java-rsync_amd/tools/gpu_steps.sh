@@ -8,7 +8,7 @@
 #   tests-batch  the batched-scan suite and the config-4 oracle checks
 #   pytest       the GPU tests named in PYTEST_ARGS (files / -k expressions)
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench line (config 5, with companions)
+#   bench        the full bench line (bench.py --full: config 5 with companions, config 4, CPU baselines)
 #   files        the config-4 line, both basis forms (FILES_STEPS steps)
 #   files-trace  one traced config-4 step (VARIANT, default half; FT_ARGS: more bench args): the chain walk's breakdown
 #   prof         rocprofv3 kernel trace + stats of the default line (the summary committed under profiles/)
@@ -78,11 +78,11 @@ for step in "$@"; do
         kb-gather) KBENCH_GATHER=1048576 run 180 "$K" 4096 0 0 5 0 1 2 3 4 5 6 0 1 2 3 4 5 6 > "$O/kb_gather.log" 2>&1 ;;
         e2e4) run 900 python java-rsync_amd/tools/e2e_config4.py $E2E4_ARGS > "$O/e2e_config4.json" 2> "$O/e2e_config4.err" ;;
         smoke) run 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1 ;;
-        bench) run 300 python bench.py > "$O/bench.json" 2> "$O/bench.err" ;;
-        hl) run 240 python bench.py --no-companions --no-files --no-cpu-baseline --steps 20 --warmup 5 $HL_ARGS \
+        bench) run 300 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" ;;
+        hl) run 240 python bench.py --full --no-companions --no-files --no-cpu-baseline --steps 20 --warmup 5 $HL_ARGS \
             > "$O/hl.json" 2> "$O/hl.err" ;;
         hl-trace) (cd /tmp && export TMPDIR=/tmp && run 300 rocprofv3 --kernel-trace --memory-copy-trace -d "$O/hl_trace" \
-            -o run --output-format csv -- python3 "$R/bench.py" --no-companions --no-files --no-cpu-baseline --steps 10 \
+            -o run --output-format csv -- python3 "$R/bench.py" --full --no-companions --no-files --no-cpu-baseline --steps 10 \
             --warmup 3 $HL_ARGS > "$O/hl_trace.json" 2> "$O/hl_trace.err") || exit 1
             python3 java-rsync_amd/tools/step_gaps.py "$O/hl_trace" > "$O/hl_gaps.txt" 2>&1 ;;
         files)
@@ -93,14 +93,14 @@ for step in "$@"; do
         files-trace) run 300 python bench.py --workload files --variant "$VARIANT" --steps 1 --warmup 1 --no-cpu-baseline \
             --no-companions --opt scan_trace=2 $FT_ARGS > "$O/files_${VARIANT}_trace.json" 2> "$O/files_${VARIANT}_trace.err" ;;
         prof) (cd /tmp && export TMPDIR=/tmp && run 300 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run \
-            --output-format csv -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline \
+            --output-format csv -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline \
             > "$O/prof_bench.json" 2> "$O/prof_bench.err") || exit 1 ;;
         timeline) (cd /tmp && export TMPDIR=/tmp && run 300 rocprofv3 --kernel-trace --memory-copy-trace --stats \
             -d "$O/timeline" -o run --output-format csv -- python3 "$R/bench.py" --workload files --variant "$VARIANT" \
             --steps 3 --warmup 1 --no-cpu-baseline --no-companions $TL_ARGS > "$O/timeline.json" 2> "$O/timeline.err") || exit 1 ;;
         fetch)
             (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -d "$O/fetch" -o run \
-                --output-format csv -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-companions \
+                --output-format csv -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-companions \
                 > "$O/fetch_bench.json" 2> "$O/fetch_bench.err") || exit 1
             (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE -d "$O/fetch_files" -o run \
                 --output-format csv -- python3 "$R/bench.py" --workload files --steps 2 --warmup 1 --no-cpu-baseline \
@@ -129,7 +129,7 @@ for step in "$@"; do
             run 120 "$K" 16384 131072 4 8 1000 > "$O/kbench_128k.log" 2>&1
             run 120 "$K" 16384 8192 3 8 1000 1002 1005 > "$O/kbench_8k.log" 2>&1 ;;
         multi)
-            run 300 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-companions \
+            run 300 python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-companions \
                 > "$O/multi_file.json" 2> "$O/multi_file.err"
             run 300 python bench.py --gpus 2 --workload files --steps 5 --warmup 2 --no-cpu-baseline --no-companions \
                 > "$O/multi_files.json" 2> "$O/multi_files.err" ;;
@@ -138,7 +138,7 @@ for step in "$@"; do
                 run 400 python bench.py --workload files --variant "$VARIANT" --devices $d --files $((128 / d)) --steps 3 \
                     --warmup 1 > "$O/devices_$d.json" 2> "$O/devices_$d.err"
             done ;;
-        config3) run 300 python bench.py --size-gib 64 --digest 5 --steps 3 --warmup 1 --no-companions --no-cpu-baseline \
+        config3) run 300 python bench.py --full --size-gib 64 --digest 5 --steps 3 --warmup 1 --no-companions --no-cpu-baseline \
             > "$O/config3.json" 2> "$O/config3.err" ;;
         receiver) run 300 python bench.py --workload receiver --steps 2 --warmup 1 > "$O/receiver.json" 2> "$O/receiver.err" ;;
         e2e) run 400 python java-rsync_amd/tools/e2e.py --gib 16 > "$O/e2e_16GiB.json" 2> "$O/e2e.err" ;;
@@ -155,7 +155,7 @@ for step in "$@"; do
         libab)
             for r in $(seq 1 "${REPS:-2}"); do
                 for l in $LIBS; do
-                    RSH_LIB="$R/java-rsync_amd/lib/ab/$l/librsynchip.so" run 300 python bench.py $AB_ARGS --steps 20 \
+                    RSH_LIB="$R/java-rsync_amd/lib/ab/$l/librsynchip.so" run 300 python bench.py --full $AB_ARGS --steps 20 \
                         --warmup 5 --no-cpu-baseline --no-companions > "$O/${l}_$r.json" 2> "$O/${l}_$r.err"
                 done
             done ;;
@@ -178,8 +178,8 @@ for step in "$@"; do
             OPTS=""
             for o in $AB_OPTS; do OPTS="$OPTS --opt $o"; done
             for r in $(seq 1 "${REPS:-3}"); do
-                RSH_LIB="$DIAG_LIB" run 300 python bench.py $AB_ARGS --steps 20 --warmup 5 --no-cpu-baseline --no-companions > "$O/a_$r.json" 2> "$O/a_$r.err"
-                RSH_LIB="$DIAG_LIB" run 300 python bench.py $AB_ARGS --steps 20 --warmup 5 --no-cpu-baseline --no-companions $OPTS > "$O/b_$r.json" 2> "$O/b_$r.err"
+                RSH_LIB="$DIAG_LIB" run 300 python bench.py --full $AB_ARGS --steps 20 --warmup 5 --no-cpu-baseline --no-companions > "$O/a_$r.json" 2> "$O/a_$r.err"
+                RSH_LIB="$DIAG_LIB" run 300 python bench.py --full $AB_ARGS --steps 20 --warmup 5 --no-cpu-baseline --no-companions $OPTS > "$O/b_$r.json" 2> "$O/b_$r.err"
             done ;;
         *) echo "unknown step $step"; exit 2 ;;
     esac

@@ -123,6 +123,48 @@ def test_rank_device_plan(monkeypatch):
         shard.rank_device(0, 1, 0)
 
 
+def _bench_module():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_bench_dump_outputs_files(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the four .npy files hold the step's results exactly (float64 / float32), the same
+    bytes on every call, and an array over its share of the size limit is cut to the same rows every time."""
+    import numpy as np
+    import rsync_hip as R
+    b = _bench_module()
+    rng = np.random.default_rng(7)
+    C, dl = 1000, 5
+    weak = rng.integers(-2 ** 31, 2 ** 31, C, dtype=np.int64).astype(np.int32)
+    strong = rng.integers(0, 256, (C, dl), dtype=np.int64).astype(np.uint8)
+    ev = np.zeros(3, R.EVENT_DTYPE)
+    ev["offset"], ev["length"] = [0, 1 << 34, (1 << 34) + 77], [1 << 34, 77, 1 << 17]
+    ev["kind"], ev["index"], ev["count"] = [2, 1, 2], [0, 0, 131071], [131072, 0, 1]
+    b.dump_outputs(str(tmp_path / "a"), weak, strong, ev, 77, (1 << 34) + (1 << 17))
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["events.npy", "strong.npy", "totals.npy", "weak.npy"]
+    assert got["weak.npy"].dtype == np.float64 and np.array_equal(got["weak.npy"], weak)
+    assert got["strong.npy"].dtype == np.float32 and np.array_equal(got["strong.npy"], strong)
+    assert got["events.npy"].dtype == np.float64 and got["events.npy"].tolist() == [
+        [0, 1 << 34, 2, 0, 131072], [1 << 34, 77, 1, 0, 0], [(1 << 34) + 77, 1 << 17, 2, 131071, 1]]
+    assert got["totals.npy"].tolist() == [3, 77, (1 << 34) + (1 << 17)]
+    # over the limit: a fixed sample of the rows, in order, identical from call to call
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 4 * 800)  # 800 bytes per array: 100 of weak's rows, 40 of strong's
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), weak, strong, ev[:0], 0, 0)
+    cut = {f: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert all(np.array_equal(x, np.load(tmp_path / "c" / f)) for f, x in cut.items())
+    assert cut["weak.npy"].shape == (100,) and cut["strong.npy"].shape == (40, dl)
+    assert cut["events.npy"].shape == (0, 5) and sum(x.nbytes for x in cut.values()) <= 4 * 800
+    rows = np.flatnonzero(np.isin(weak, cut["weak.npy"]))
+    assert rows.size == 100 and np.array_equal(weak[rows], cut["weak.npy"])  # rows of the array, in its order
+
+
 def test_bench_traffic_profiles_name_the_kernels():
     """bench.py's roofline.traffic comes from committed FETCH_SIZE passes (profiles/, rocprofv3 --pmc): the kernel names
     it looks for must be the ones those passes recorded, for both lines (a renamed instantiation once left the config-4
