@@ -4,15 +4,10 @@
  *
  * The library's tunables and diagnostic switches (java-rsync_amd/csrc/options.h) have compiled-in defaults and
  * are never read from the environment.  The table is per process and applies to calls that start after a change.
- *  - settable in every build (tests force rare paths with them; a few are tunables): k1_gather, k1_shift,
- *    k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
- *    file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
- *    fault_inject;
- *  - A/B switches, settable only in the diagnostics build (make diag: lib/diag/librsynchip.so, loaded by the
- *    tools through RSH_LIB); the product library answers RSH_E_INVAL and runs their defaults: scan_diag,
- *    scan_phase, scan_phase_guess, scan_preprobe, scan_sample, scan_spec_order, scan_early, scan_wait,
- *    scan_defer_steps, scan_defer_us, scan_spec_queue, scan_flags_host, scan_prep_pieces, time_spec, batch_spec,
- *    batch_spin_us, batch_readahead, batch_prep_all, batch_chain_overlap, batch_skip_rest, chain_help_tiles.
+ * Tests force rare paths with them; a few are tunables: k1_gather, k1_shift,
+ * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
+ * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
+ * fault_inject.
  */
 #ifndef RSYNC_HIP_DEBUG_H
 #define RSYNC_HIP_DEBUG_H
@@ -25,7 +20,7 @@
 extern "C" {
 #endif
 
-/* RSH_OK, or RSH_E_INVAL for an unknown name or an A/B switch in the product build. */
+/* RSH_OK, or RSH_E_INVAL for an unknown name. */
 int rsh_debug_set_option(const char* name, int64_t value);
 int rsh_debug_get_option(const char* name, int64_t* value);
 /* Every option back to its compiled-in default. */

@@ -95,14 +95,14 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
     uint32_t ngroups = plan_block_sums_files(k1.data(), NF, &plans, &lanes, &lane_align, &partial);
     RSH_BHIP(S->ensure_file_abort(NF));
     for (K1Plan& pl : plans) pl.abort = S->file_abort + pl.file;
-    // The chain walk (option batch_chain, with the default speculation policy) runs after the speculation.  Two
+    // The chain walk (option batch_chain) runs after the speculation.  Two
     // phases (option batch_chain_prefix): the speculation over each file's first na_a windows -- a quarter round of
     // the chip's wave slots over the whole batch (256 windows per file for config 4's 128 files: its 50%-modified
     // walks all end inside 2 MiB; a full round, 1024, cost that step 0.3 ms of prefix K1 and the identical one
     // 0.065 ms less, round 5 r5z6/r5z7) -- and a walk over them; then the rest of the speculation for the
     // files whose walk reached the prefix's end (the others' groups stop at once: the walk wrote their abort words)
     // and a second walk.  A file that leaves the synced state early (an edit) costs its prefix, not its whole length.
-    const bool chain_on = opt(OPT_BATCH_CHAIN) != 0 && opt(OPT_BATCH_SPEC) == -1;
+    const bool chain_on = opt(OPT_BATCH_CHAIN) != 0;
     const int32_t kChainEvents = (int32_t)std::clamp<int64_t>(
         kChainEventBytes / ((int64_t)std::max<int32_t>(NF, 1) * (int64_t)sizeof(rsh_event)), 256, kChainEventsMax);
     bool two_phase = false;
@@ -222,9 +222,8 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
     }
     // the speculation K1 waits for the lead sums only (a VALU-heavy kernel beside it slows the waves that share
     // its SIMDs, and the slowest wave ends the launch); the tables' download and the probe hashes follow it on
-    // the context stream and run beside the speculation (option scan_spec_order = 0, A/B: all of it beside)
-    const bool spec_after_prep = opt(OPT_SCAN_SPEC_ORDER) != 0;
-    if (spec_after_prep) RSH_BHIP(hipEventRecord(c->ev_prep, st));
+    // the context stream and run beside the speculation
+    RSH_BHIP(hipEventRecord(c->ev_prep, st));
     // (stream) the received tables, to pinned host memory in one kernel
     CopyEnt* tc = S->h_copies.as<CopyEnt>();
     int64_t max_tab = 0;
@@ -238,10 +237,8 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
         max_tab = std::max<int64_t>(max_tab, (int64_t)fs.C * 4);
     }
     // with the speculation after the lead sums, the table work below runs beside its K1: background launches
-    // (priority 0, a few hundred workgroups; the download is PCIe-bound anyway).  Option batch_prep_all = 1
-    // (A/B): the speculation after all of it, full-width launches.
-    const bool prep_all = opt(OPT_BATCH_PREP_ALL) != 0;
-    const bool bg = spec_after_prep && !prep_all;
+    // (priority 0, a few hundred workgroups; the download is PCIe-bound anyway)
+    constexpr bool bg = true;
     // (chain walks: the host tables and the probe hashes serve the resolvers only -- built after the walks, for
     // the files they leave)
     if (!chain_on) RSH_BHIP(launch_copy_many(tc, ntc, max_tab, st, bg));  // stream order: after whatever produced them
@@ -281,7 +278,6 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
         }
         RSH_BHIP(launch_chunk_index(ke, (uint32_t)NF, (int32_t)maxC, st, bg));
     }
-    if (spec_after_prep && prep_all) RSH_BHIP(hipEventRecord(c->ev_prep, st));
 
     // the batched aligned speculation (deferred; see scan_device in capi.cpp)
     int gen = c->next_gen();  // a stopped tentative launch's generation; a later launch takes a new one
@@ -329,7 +325,7 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
         RSH_BHIP(hipEventRecord(S->ev_scopy, aux));
         S->scopy_pending = true;
         // the sources may come from work on the context stream (and the lead sums go first, see above)
-        RSH_BHIP(hipStreamWaitEvent(aux, (spec_after_prep && !chain_on) ? c->ev_prep : c->ev_in, 0));
+        RSH_BHIP(hipStreamWaitEvent(aux, chain_on ? c->ev_in : c->ev_prep, 0));
         RSH_BHIP(launch_block_sums_batch(S->k1_groups.as<K1Group>(), ngroups, S->k1_lanes.as<K1Lane>(),
                                          (uint32_t)lanes.size(), lane_align, seed_word(seed), aux, c->abort_word, gen,
                                          partial));
@@ -377,21 +373,12 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
         return RSH_OK;
     };
 
-    // policy (A/B via option batch_spec; the default (-1), measured best on config 4, is head mode with the
-    // launch after kDeferRounds rounds): -2 "early" = the speculation's K1 starts now, beside whatever the
-    // device is still doing (e.g. the Generator), resolvers in head mode until it lands; -3 "wait" = as
-    // early, but the resolvers start only once it has landed; N >= 0 = launch after N rounds
-    const int64_t pol_v = opt(OPT_BATCH_SPEC);
-    const bool pol = pol_v != -1;
-    const bool wait_spec = pol_v == -3;
-    const bool early_spec = pol_v == -2 || wait_spec;
-    const int defer_rounds = (pol && !early_spec) ? (int)std::max<int64_t>(0, pol_v) : kDeferRounds;
-    // launch-then-confirm (default policy): the speculation K1 is launched now, behind the Generator's work;
-    // the lead check below keeps it for the files whose first windows carry their chunks' sums (they wait for
-    // it instead of taking head-mode rounds) or stops it when no file qualifies
-    const bool early_on = opt(OPT_SCAN_EARLY) != 0;  // A/B
-    const bool tentative = !pol && early_on && nlead_all > 0 && !chain_on;
-    if (early_spec || tentative) {
+    // Without the chain walk the policy (measured best on config 4) is head mode with the launch after kDeferRounds
+    // rounds, and launch-then-confirm: the speculation K1 is launched now, behind the Generator's work; the lead check
+    // below keeps it for the files whose first windows carry their chunks' sums (they wait for it instead of taking
+    // head-mode rounds) or stops it when no file qualifies
+    const bool tentative = nlead_all > 0 && !chain_on;
+    if (tentative) {
         const int r = launch_spec_k1();
         if (r != RSH_OK) return r;
     }
@@ -542,7 +529,7 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
                               mw > 0 ? S->chain_map.as<unsigned long long>() + map_off[(size_t)f] : nullptr, hend,
                               kslots_dup(S, tns) + fs.off_tw};
             if (chh) chh[f] = ChainHelp{(int32_t)((hend + CHAIN_MAP_SEG - 1) / CHAIN_MAP_SEG), 0, 1, 0, 0, 0, 0, 0, INT64_MAX, 0, 0, 0,
-                                        (int32_t)opt(OPT_CHAIN_HELP_TILES)};
+                                        kChainHelpTiles};
         }
         const uint32_t n_help = !map_on ? 0u
                                 : helpers_opt > 0 ? (uint32_t)helpers_opt
@@ -605,20 +592,17 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
             RSH_BHIP(launch_chain_advance(cf, (uint32_t)NF, st, 0, gen_b, map_on ? S->chain_help.as<ChainHelp>() : nullptr,
                                           n_help, tr));
             RSH_BHIP(hipEventRecord(S->ev_wa, st));
-            // (option batch_skip_rest) once phase 0 has ended, the rest of the speculation only if some walk reached
+            // Once phase 0 has ended, the rest of the speculation only if some walk reached
             // the prefix's end (CHAIN_MORE): otherwise every file is done, or left to its resolver with the prefix
             // speculated, and the rest's launch -- all its groups stopping at once, ~0.17 ms of dispatch for config 4's
             // 30720 -- its flags and phase 1 are skipped.  The host waits for phase 0 either way (a few us more before
             // the rest's launch when it is needed).
-            if (opt(OPT_BATCH_SKIP_REST) != 0 && opt(OPT_BATCH_CHAIN_OVERLAP) == 0) {
-                RSH_BHIP(await_walks());
-                skip_rest = true;
-                for (int32_t f = 0; f < NF && skip_rest; ++f) skip_rest = co[f].status != CHAIN_MORE;
-            }
+            RSH_BHIP(await_walks());
+            skip_rest = true;
+            for (int32_t f = 0; f < NF && skip_rest; ++f) skip_rest = co[f].status != CHAIN_MORE;
             if (!skip_rest) {
-                // the rest of the speculation after the walks (the groups of files they finished stop at once), or
-                // (option batch_chain_overlap) beside them: no gap after the prefix's K1, but the walks share the chip
-                if (opt(OPT_BATCH_CHAIN_OVERLAP) == 0) RSH_BHIP(hipStreamWaitEvent(aux, S->ev_wa, 0));
+                // the rest of the speculation after the walks (the groups of files they finished stop at once)
+                RSH_BHIP(hipStreamWaitEvent(aux, S->ev_wa, 0));
                 RSH_BHIP(launch_block_sums_batch(S->k1_groups.as<K1Group>() + ng_a, ng_b, S->k1_lanes.as<K1Lane>() + nla,
                                                  (uint32_t)nlb, align_b, seed_word(seed), aux, c->abort_word, gen_b,
                                                  partial_b));
@@ -766,27 +750,11 @@ int scan_batch(rsh_ctx* c, rsh_scan_job* jobs, const std::vector<int32_t>& which
         }
         if (trace) fprintf(stderr, "[rsh-batch] lead check: %d of %d files wait for the speculation\n", nwait, NF);
     }
-    if (early_spec && !wait_spec) {
-        spec_rc = launch_spec();  // the tail (flags, downloads) behind the K1 already running
-        if (spec_rc != RSH_OK) return spec_rc;
-        spec_launched = true;
-    }
-    if (wait_spec) {
-        spec_rc = launch_spec();
-        if (spec_rc != RSH_OK) return spec_rc;
-        spec_launched = true;
-        RSH_BHIP(hipEventSynchronize(c->ev_spec));
-        if (trace) fprintf(stderr, "[rsh-batch] speculation landed at %.3f ms\n", ms_since(t0));
-        b.landed.store(true);
-        b.aligned.store(true);
-        for (FileScan& fs : files) fs.be.head = false;
-    }
 
     RoundCtl ctl;
     ctl.launch_spec = launch_spec;
     ctl.spec_launched = &spec_launched;
     ctl.spec_rc = &spec_rc;
-    ctl.defer_rounds = defer_rounds;
     ctl.k1_launched = k1_launched;
     ctl.gen = gen;
     ctl.trace = trace;

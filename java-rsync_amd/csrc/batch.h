@@ -199,6 +199,8 @@ namespace batch {
 
 constexpr int32_t kMaxLive = 256;     // files resolved concurrently (one host thread each)
 constexpr int kDeferRounds = 2;       // rounds in head mode before the speculation is launched
+constexpr int32_t kChainHelpTiles = 1;  // tiles a phase-0 walk searches before helpers map ahead of it (ChainHelp)
+constexpr int kSpinUs = 200;          // round hand-offs: a waiter spins this long before it blocks (spin_wait)
 constexpr int32_t kMaxWorkers = 32;   // host threads running the resolvers
 constexpr size_t kFiberStack = 512 * 1024;
 constexpr int32_t kEagerSortChunks = 1 << 16;  // tables up to this size are sorted before the first round
@@ -285,11 +287,6 @@ class BatchBackend : public ScanBackend {
     int64_t t_pos = -1;    // the last hit returned: its weak sum t_val is known
     int32_t t_val = 0;
     HitCache cache;
-    // read-ahead of window requests: the bytes [pf_pos, pf_pos + pf.size()) of the source, copied with the
-    // last window request; a later digest inside them needs no round trip (in head mode the next match of
-    // a chain, or of every other block, is usually a window or two further on)
-    std::vector<uint8_t> pf;
-    int64_t pf_pos = -1;
 
     int64_t aligned_count() override;
     int64_t flags_count() override { return head ? 0 : na; }
@@ -380,15 +377,13 @@ inline FileScan& scan_of(Batch* b, int32_t f) { return (*b->files)[(size_t)f]; }
 inline int64_t BatchBackend::aligned_count() { return (head || !b->aligned.load(std::memory_order_acquire)) ? 0 : na; }
 
 // Round hand-offs: a blocked thread takes ~50 us to wake from a condition variable, once per round per
-// side (coordinator -> workers, last worker -> coordinator).  Waiters spin up to RSH_BATCH_SPIN us
-// (option batch_spin_us, default 200; 0 = block at once) on the predicate first, then block as before; the
-// predicate is re-checked under the mutex either way, so the hand-off protocol is unchanged.
-inline int spin_us() { return (int)std::max<int64_t>(0, opt(OPT_BATCH_SPIN_US)); }
+// side (coordinator -> workers, last worker -> coordinator).  Waiters spin up to kSpinUs microseconds on the
+// predicate first, then block as before; the predicate is re-checked under the mutex either way, so the hand-off
+// protocol is unchanged.
 template <class Pred>
 void spin_wait(Pred pred) {
-    const int us = spin_us();
-    if (us <= 0 || pred()) return;
-    const auto end = std::chrono::steady_clock::now() + std::chrono::microseconds(us);
+    if (pred()) return;
+    const auto end = std::chrono::steady_clock::now() + std::chrono::microseconds(kSpinUs);
     for (uint32_t i = 1;; ++i) {
         __builtin_ia32_pause();
         if (pred()) return;
@@ -408,12 +403,11 @@ hipError_t serve_round(rsh_ctx* c, BatchState* S, std::vector<FileScan>& files, 
                        hipStream_t st);
 
 // What the resolver pool's coordinator needs from scan_batch: the deferred speculation launch (launched after
-// defer_rounds rounds unless it already runs) and the state it shares with scan_batch.
+// kDeferRounds rounds unless it already runs) and the state it shares with scan_batch.
 struct RoundCtl {
     std::function<int()> launch_spec;
     bool* spec_launched = nullptr;
     int* spec_rc = nullptr;
-    int defer_rounds = 0;
     bool k1_launched = false;  // the speculation's K1 runs: cancel resolved files' groups (file_abort)
     int gen = 0;               // ... with this generation
     bool trace = false;

@@ -100,11 +100,9 @@ void BatchBackend::flush_gather(const int64_t* tpos, int64_t nt, int32_t* tv, co
     b->post(fs);
 }
 
-// bytes copied per window request (A/B option batch_readahead; never less than the window).  Off by
-// default: on config 4 it cut the rounds from 23 to 18, but the head-mode rounds it removed were cheap
-// window copies and the probes left in their place wait behind the speculation K1
-int64_t readahead_bytes() { return std::max<int64_t>(0, opt(OPT_BATCH_READAHEAD)); }
-
+// A window request copies the window only.  Reading ahead cut config 4's rounds from 23 to 18, but the head-mode
+// rounds it removed were cheap window copies and the probes left in their place wait behind the speculation K1
+// (DESIGN.md sec. 5a).
 void BatchBackend::md5_at(int64_t p, uint8_t out[16]) {
     const int64_t w = std::min<int64_t>(B, n - p);
     const uint8_t* src = nullptr;
@@ -113,22 +111,15 @@ void BatchBackend::md5_at(int64_t p, uint8_t out[16]) {
         for (int k = 0; k < HIT_WINDOWS; ++k)
             if (p == win_pos[k]) src = hit + 16 + (int64_t)k * B;  // came back with the probe result
     }
-    if (!src && pf_pos >= 0 && p >= pf_pos && p + w <= pf_pos + (int64_t)pf.size()) src = pf.data() + (p - pf_pos);
     if (!src) {
         FileScan& fs = scan_of(b, f);
-        const int64_t ext = std::min<int64_t>(std::max<int64_t>(w, readahead_bytes()), n - p);
         fs.req = Req{};
         fs.req.kind = Req::WIN;
         fs.req.p = p;
-        fs.req.w = ext;
-        bytes_read += ext;
+        fs.req.w = w;
+        bytes_read += w;
         b->post(fs);
         src = fs.req.win;
-        if (ext > w) {  // keep the read-ahead (the round's window buffer is reused by the next round)
-            pf.assign(src, src + ext);
-            pf_pos = p;
-            src = pf.data();
-        }
     }
     const auto t0 = std::chrono::steady_clock::now();
     HostMd5 h;  // one serial chain per window: on this file's host thread, beside the other files' work
@@ -534,12 +525,11 @@ hipError_t run_resolvers(rsh_ctx* c, BatchState* S, const std::shared_ptr<Batch>
     bool& spec_launched = *ctl.spec_launched;
     int& spec_rc = *ctl.spec_rc;
     auto& launch_spec = ctl.launch_spec;
-    const int defer_rounds = ctl.defer_rounds;
     const bool k1_launched = ctl.k1_launched;
     const int gen = ctl.gen;
     const int ncpu = WorkerCap::value() > 0 ? std::min(call_cores(), WorkerCap::value()) : call_cores();
     // spinning waiters: one core stays free for the coordinator
-    const int32_t ncores = (spin_us() > 0 && ncpu > 2) ? ncpu - 1 : ncpu;
+    const int32_t ncores = ncpu > 2 ? ncpu - 1 : ncpu;
     // only the files still live get a worker: after the chain walks (or a leading speculation) most files are
     // done, and a worker per core spinning for one live file's rounds only eats the CPU quota
     std::vector<int32_t> live;
@@ -640,7 +630,7 @@ hipError_t run_resolvers(rsh_ctx* c, BatchState* S, const std::shared_ptr<Batch>
             }
         }
         ++rounds;
-        if (!spec_launched && rounds > defer_rounds) {
+        if (!spec_launched && rounds > kDeferRounds) {
             spec_rc = launch_spec();
             spec_launched = true;
         }

@@ -193,7 +193,7 @@ struct rsh_ctx {
     hipEvent_t ev_gen_a = nullptr, ev_gen_b = nullptr;  // timing: rsh_block_sums_device's K1 (rsh_debug_kernel_ms)
     bool gen_timed = false;                             // ... recorded by the last rsh_block_sums_device
     bool spec_timed = false;                            // ev_k1a / ev_k1b belong to the last scan's speculation
-    hipEvent_t ev_rs_tail = nullptr;  // scan_spec_queue: the end of a scan's work on aux (see spec_buffers_free)
+    hipEvent_t ev_rs_tail = nullptr;  // the end of a single-file scan's work on aux (see spec_buffers_free)
     hipEvent_t ev_pha[2] = {nullptr, nullptr}, ev_phb[2] = {nullptr, nullptr};  // timing: set i's phase K1 (stats)
     int ph_set = 0;  // the buffer set of the latest phase launch
     PinnedBuf h_weak, h_strong, h_aw, h_as, h_fl;
@@ -210,7 +210,7 @@ struct rsh_ctx {
     PinnedBuf h_files;   // the scan's rsh::ScanFile (a batch of one for the probe / gather kernels)
     PinnedBuf h_stage;   // file ingest ring (ingest.cpp); never shared with the scan's buffers
     PinnedBuf h_rcv_ops[2];  // rsh_receiver_combine_batch: the gather ops of a pass, staged
-    PinnedBuf h_prep;        // the prep launch's outputs (scan_spec_queue)
+    PinnedBuf h_prep;        // the prep launch's outputs (scan_device)
     PinnedBuf h_stamps;      // the stamped launches' stamps, one 64-B line each
     PinnedBuf h_fgw, h_fjobs, h_fout;  // flush_probe: the chain's gather list, its job, its outputs
     uint64_t first_used = 0;    // probe result slots handed out (see HipBackend::first_hit)

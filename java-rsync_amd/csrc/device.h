@@ -139,7 +139,7 @@ hipError_t launch_chain_flags_stamped(const int32_t* d_wsrc, const uint8_t* d_ss
                                       const uint8_t* d_sbas, uint32_t count, uint32_t dl, uint8_t* h_flags,
                                       Stamp st, hipStream_t s);
 // The single-file scan's launch decision in one launch on the speculation's queue, ahead of it (scan_device,
-// scan_spec_queue): the weak sums T(kB) of the sampled windows wins[i] (each window split over `pieces` workgroups,
+// the prep launch): the weak sums T(kB) of the sampled windows wins[i] (each window split over `pieces` workgroups,
 // partial sums added with device atomics into scratch, 2 ints per sample, zero before the launch), the received
 // table's weak sums at the same chunks, and window 0's bytes, all into pinned host memory, then the stamp.
 struct ScanPrep {
@@ -406,7 +406,7 @@ struct ChainHelp {
     int64_t t_kset;            // wall-clock ticks spent building this file's key set in helpers (trace)
     int32_t whole;             // segments mapped whole, before the walk reached them (trace)
     int32_t nhelp;             // helpers currently on this file
-    int32_t help_tiles;        // tiles the walk searches before helpers join it (A/B switch chain_help_tiles: 1; 4 until
+    int32_t help_tiles;        // tiles the walk searches before helpers join it (batch.h kChainHelpTiles: 1; 4 until
                                // round 5, 4.625 against 4.57 ms for config 4 half, r5m4)
 };
 constexpr int CHAIN_THREADS = 512;                      // 8 waves (2 per SIMD: 256 VGPRs each)

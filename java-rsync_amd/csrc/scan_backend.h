@@ -39,8 +39,8 @@ inline hipError_t copy_to_host(std::initializer_list<rsh::CopyEnt> ents, hipStre
     return rsh::launch_copy_few(f, s);
 }
 constexpr int kScanWindows = 2;  // hit windows per probe in the single-file scan (hit_cache.h)
-// Head mode launches the aligned speculation after scan_defer_steps (4) resolver steps or scan_defer_us (500 us;
-// options.h) ...
+// Head mode launches the aligned speculation after kDeferSteps resolver steps or kDeferUs microseconds ...
+constexpr int64_t kDeferSteps = 4, kDeferUs = 500;
 constexpr int64_t kChainSteps = 2;  // ... after this many steps when the last event is a run of matches
 // ... or at once when the first kLeadWindows (ctx.h) aligned source windows all carry chunk k's weak sum
 // ... over the windows up to the last of scan_samples (256; 1024 until round 2: the same step time, r2_ab2)
@@ -57,8 +57,8 @@ class HipBackend : public rsh::ScanBackend {
         memcpy(seed_, seed, 4);
     }
     hipError_t err = hipSuccess;
-    // the queue of the round trips (and of the tiled scan's loads): the context stream, or aux when the
-    // speculation runs on the context stream (option scan_spec_queue, scan_device)
+    // the queue of the round trips (and of the tiled scan's loads): the context stream, or aux in scan_device, whose
+    // speculation runs on the context stream
     hipStream_t rs_;
     int64_t na = 0;
     const int32_t* aw = nullptr;  // pinned host copies of the aligned speculation
@@ -80,7 +80,7 @@ class HipBackend : public rsh::ScanBackend {
         if (head) return 0;
         if (!sums_ready) {
             if (lazy_na >= 0) {
-                // scan_spec_queue: the first step that needs them downloads them (on rs_; the flags have landed) and
+                // the first step that needs them downloads them (on rs_; the flags have landed) and
                 // waits: the copy is tens of microseconds, the generic path's probe and host digest as long or longer
                 CallTrace tr("sums_dl", lazy_na);
                 ok(hipStreamWaitEvent(rs_, c_->ev_flags, 0));
@@ -471,7 +471,7 @@ class HipBackend : public rsh::ScanBackend {
         // windows wholly in the data the device holds: the rest of the file, or of the tile
         const int64_t hi = tiled ? std::min(n_, tile_lo + tile_T + tile_H) : n_;
         const int64_t count = hi == n_ ? (n_ - s + B_ - 1) / B_ : (hi - s - B_) / B_ + 1;
-        if (count < kPhaseMinWindows || ph_launches >= kPhaseMaxLaunches || err != hipSuccess || !phase_on()) return;
+        if (count < kPhaseMinWindows || ph_launches >= kPhaseMaxLaunches || err != hipSuccess) return;
         phase_stop();  // one at another phase is dead work now
         CallTrace tr("phase_spec", s);
         ph_gen_ = c_->next_gen();
@@ -548,7 +548,6 @@ class HipBackend : public rsh::ScanBackend {
         ph_s0_ = -1;
         ph_landed_ = false;
     }
-    static bool phase_on() { return rsh::opt(rsh::OPT_SCAN_PHASE) != 0; }  // A/B: 0 = no phase speculation
 
   private:
     static constexpr int64_t kPhaseMinWindows = 8;    // shorter remainders resolve faster on the generic path

@@ -5,7 +5,7 @@ Runs the bench's step (rsh_block_sums_device + rsh_match_scan_device over a resi
 timestamps around each call.  Each --ab is an option set ("name=value,name=value"; "" = the defaults); the sets run
 interleaved, --reps rounds of --steps steps each, and the line reports per set the median host time of the Generator
 call, the scan call, the Generator K1 query (rsh_debug_kernel_ms) and the whole step, per round.
-usage: python hl_host.py [--steps 20] [--reps 3] [--ab "" --ab "scan_spec_queue=0"]
+usage: python hl_host.py [--steps 20] [--reps 3] [--ab "" --ab "time_gen=0"]
 """
 import argparse
 import ctypes

@@ -107,9 +107,18 @@ def test_sender_large_table_desync(ctx):
 
 
 @pytest.mark.parametrize("blen,dlen,mode", [(65536, 4, "identical"), (65536, 4, "half"), (131072, 4, "half"),
-                                            (8192, 3, "insert")])
+                                            (8192, 3, "insert"), (512, 2, "empty_table")])
 def test_sender_config_shapes(ctx, blen, dlen, mode):
-    """BASELINE config shapes at 64-128 MiB: identical basis, every-other-block modified basis, insertion."""
+    """BASELINE config shapes at 64-128 MiB: identical basis, every-other-block modified basis, insertion.
+    empty_table: 7 windows and a tail against a table of no chunks (an empty replica, B = 512): there is no lead
+    window, so no speculation is launched before the resolver starts, and the scan ends in its first head-mode step,
+    as one literal run like the oracle's, without needing one (speculation_aborted == 2).  Only an empty table
+    reaches that branch below 131072 windows, and only a scan of fewer than four steps -- under 40 windows -- ends
+    before the deferred launch (300 windows: 31 flushes, the launch after the fourth, speculation_aborted == 0)."""
+    if mode == "empty_table":
+        st = _sender_both(ctx, b"", O.splitmix(7 * blen + 77, 0x5EED5EED000000E2).tobytes(), blen, dlen)
+        assert st["speculation_aborted"] == 2 and st["phase_launches"] == 0, st
+        return
     n = 64 << 20
     basis = O.splitmix(n, 0x5EED5EED00000005)
     if mode == "identical":
