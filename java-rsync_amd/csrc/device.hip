@@ -272,8 +272,8 @@ __device__ __forceinline__ int poll_abort(const int* flag) {
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
 
-// The production MD5 step form (md5_asm.inc: 16 steps per asm statement, no s_nop after the rotates; kbench
-// A/Bs of the other forms in DESIGN.md sec. 4)
+// The production MD5 step form (md5_asm.inc: 16 steps per asm statement, an s_nop 0 after every step).  It is the
+// only form in the tree; the kbench A/Bs it won against the others are history in DESIGN.md sec. 4
 __device__ __forceinline__ void md5_stream_block(Md5State& st, const uint32_t (&m)[16]) { md5_compress_rot16n(st, m); }
 
 // amdgpu_num_vgpr(192): two waves fill 384 of a SIMD's 512 registers, leaving room for one wave of the

@@ -299,83 +299,346 @@ __device__ __forceinline__ void chain_st64(int64_t* p, int64_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// One tile of a file's hit map: positions [q0, q0 + CHAIN_TILE) below hend, q0 a multiple of CHAIN_TILE.  The keys
-// are the walk's wide-tile keys in the synced state (each lane anchored on its block's aligned sum T(o), the prefix
-// sums from one exscan rebased at each block's first lane, the head of the block the tile starts in); bit i of
-// lane t's word = position q0 + 32 t + i hits the key set.  Stored as (gen << 32) | bits, one 8-byte store.
-__device__ void chain_map_tile(const ChainFile& F, int64_t q0, uint32_t gen, const ChainKeySet& kset, int32_t* sh,
-                               int32_t (*s_seg)[4]) {
-    const int t = threadIdx.x;
-    const int64_t n = F.n, B = F.B, hend = F.hend;
-    const int64_t kb0 = q0 / B, o0 = kb0 * B;
-    int32_t head[4] = {0, 0, 0, 0};
-    if (q0 > o0) {
-        range_sums(F.data, n, o0, q0, o0, head[0], head[1]);
-        range_sums(F.data, n, o0 + B, q0 + B, o0, head[2], head[3]);
-        block_reduce<4>(head, sh);
-    }
-    const int64_t p0 = q0 + (int64_t)t * CHAIN_PPT;
-    const int64_t kb = p0 / B, o = kb * B;
-    uint32_t xa[2][4], xb[2][4];
-    load16(F.data, n, p0, xa[0]);
-    load16(F.data, n, p0 + 16, xa[1]);
-    load16(F.data, n, p0 + B, xb[0]);
-    load16(F.data, n, p0 + B + 16, xb[1]);
-    const bool live = p0 < hend;
-    const int32_t To = live ? F.aw[kb] : 0;
-    int32_t pre[4];
-    chain_lane_sums(xa, xb, (uint32_t)(p0 - q0), (uint32_t)B, pre);
-    block_exscan<4>(pre, sh);
-    if (p0 == o) {
+// The kernel's LDS as the functions outside its body see it (chain_advance_kernel builds it once)
+struct ChainLds {
+    ChainKeySet kset;          // the table's keys
+    int32_t* sh;               // block_reduce / block_exscan
+    int32_t (*seg)[4];         // wide tiles: the exscan at each block's first lane (CHAIN_SEGS rows)
+    int32_t* hit;              // first hit in a tile (offset from the tile start), or INT_MAX
+    uint32_t* key;             // its key
+    int32_t* bk;               // bucket of the key (ascending chunk index, CHAIN_BUCKET_CAP entries)
+    int32_t* nbk;
+    int64_t* zero;             // first unset chain flag
+    unsigned long long* best;  // helpers: the file to map next
+    int32_t* word;
+    int32_t* live;
+};
+
+// A wide tile lane's keys: tile [q0, q0 + CHAIN_TILE), q0 a multiple of CHAIN_PPT, lane t's 32 positions from
+// p0 = q0 + 32 t across block boundaries.  Each lane anchors its positions on its own block's aligned sum T(o); the
+// prefix sums from o come from one exscan over the tile with weights relative to the tile start, rebased at each
+// block's first lane (a segmented scan), and the head of the block the tile starts in (range_sums from o to the
+// tile).  In the synced state these keys are the windows' true weak sums.  The walk's tile search and the hit map's
+// tiles both derive them here, so the map's bits are the walk's hits by construction.
+struct ChainTileKeys {
+    int64_t p0, kb, o, kb0;         // the lane's first position, its block and origin; the tile's first block
+    uint32_t xa[2][4], xb[2][4];    // the 32 bytes at p0 and at p0 + B
+    int32_t head[4], pre[4], To;
+};
+// ... the sums: the head of the tile's first block, the lane's bytes, T(o) (live lanes only), the lane's sums and
+// their exscan, a block's first lane leaving its rebasing point in seg.  (all threads; the caller's barrier follows)
+__device__ __forceinline__ void chain_tile_sums(ChainTileKeys& K, const ChainFile& F, int64_t q0, bool live,
+                                                const ChainLds& L) {
+    const int64_t n = F.n, B = F.B;
+    K.kb0 = q0 / B;
+    const int64_t o0 = K.kb0 * B;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) s_seg[kb - kb0][v] = pre[v];
+    for (int v = 0; v < 4; ++v) K.head[v] = 0;
+    if (q0 > o0) {
+        range_sums(F.data, n, o0, q0, o0, K.head[0], K.head[1]);
+        range_sums(F.data, n, o0 + B, q0 + B, o0, K.head[2], K.head[3]);
+        block_reduce<4>(K.head, L.sh);
     }
+    K.p0 = q0 + (int64_t)threadIdx.x * CHAIN_PPT;
+    K.kb = K.p0 / B;
+    K.o = K.kb * B;
+    load16(F.data, n, K.p0, K.xa[0]);
+    load16(F.data, n, K.p0 + 16, K.xa[1]);
+    load16(F.data, n, K.p0 + B, K.xb[0]);
+    load16(F.data, n, K.p0 + B + 16, K.xb[1]);
+    K.To = live ? F.aw[K.kb] : 0;
+    chain_lane_sums(K.xa, K.xb, (uint32_t)(K.p0 - q0), (uint32_t)B, K.pre);
+    block_exscan<4>(K.pre, L.sh);  // sums over [q0, p0) and [q0 + B, p0 + B), weights j - q0
+    if (K.p0 == K.o) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) L.seg[K.kb - K.kb0][v] = K.pre[v];
+    }
+}
+// ... the rolling value at p0 as its two 16-bit halves, kept apart (u1, u2: each exact mod 2^16, the Java
+// subtract-then-add of Rolling.java:25-60 in two adds each).  (live lanes, after the barrier)
+__device__ __forceinline__ void chain_tile_start(const ChainTileKeys& K, int64_t q0, uint32_t B,
+                                                 const int32_t (*seg)[4], uint32_t& u1, uint32_t& u2) {
+    uint32_t pa, pa2, pb, pb2;  // sums over [o, p0) and [o + B, p0 + B), weights j - o
+    if (K.o < q0) {             // the tile's first block: its head + the tile's part
+        const uint32_t d = (uint32_t)(q0 - K.o);
+        pa = (uint32_t)K.head[0] + (uint32_t)K.pre[0];
+        pa2 = (uint32_t)K.head[1] + (uint32_t)K.pre[1] + d * (uint32_t)K.pre[0];
+        pb = (uint32_t)K.head[2] + (uint32_t)K.pre[2];
+        pb2 = (uint32_t)K.head[3] + (uint32_t)K.pre[3] + d * (uint32_t)K.pre[2];
+    } else {                    // rebased at the block's first lane
+        const int32_t* R = seg[K.kb - K.kb0];
+        const uint32_t d = (uint32_t)(K.o - q0);
+        pa = (uint32_t)(K.pre[0] - R[0]);
+        pa2 = (uint32_t)(K.pre[1] - R[1]) - d * pa;
+        pb = (uint32_t)(K.pre[2] - R[2]);
+        pb2 = (uint32_t)(K.pre[3] - R[3]) - d * pb;
+    }
+    const uint32_t s1o = (uint32_t)K.To & 0xFFFFu, s2o = (uint32_t)K.To >> 16;
+    const uint32_t P1e = s1o + pb;
+    const uint32_t P2e = B * s1o - s2o + pb2;
+    u1 = P1e - pa;
+    u2 = (uint32_t)(K.p0 + B - K.o) * u1 - (P2e - pa2);
+}
+// ... and half hh's 16 keys (positions p0 + 16 hh + i), rolling u1, u2 on to the next half
+__device__ __forceinline__ void chain_tile_half(const ChainTileKeys& K, int hh, uint32_t B, uint32_t& u1, uint32_t& u2,
+                                                uint32_t (&keys)[16]) {
+    uint32_t wa[4], wb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        wa[j] = hh ? K.xa[1][j] : K.xa[0][j];
+        wb[j] = hh ? K.xb[1][j] : K.xb[0][j];
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        keys[i] = (u1 & 0xFFFFu) | (u2 << 16);
+        const int32_t xo = sbyte_of(wa, i), xi = sbyte_of(wb, i);
+        u1 += (uint32_t)(xi - xo);
+        u2 += u1 - (uint32_t)__mul24((int)B, xo);  // (B <= 2^17: a full-rate 24-bit multiply)
+    }
+}
+
+// One tile of a file's hit map: positions [q0, q0 + CHAIN_TILE) below hend, q0 a multiple of CHAIN_TILE, with the
+// walk's wide-tile keys (ChainTileKeys); bit i of lane t's word = position q0 + 32 t + i hits the key set.  Stored as
+// (gen << 32) | bits, one 8-byte store.
+__device__ void chain_map_tile(const ChainFile& F, int64_t q0, uint32_t gen, const ChainLds& L) {
+    const int64_t p0 = q0 + (int64_t)threadIdx.x * CHAIN_PPT, hend = F.hend;
+    const bool live = p0 < hend;
+    ChainTileKeys K;
+    chain_tile_sums(K, F, q0, live, L);
     __syncthreads();
     if (live) {
-        uint32_t pa, pa2, pb, pb2;
-        if (o < q0) {
-            const uint32_t d = (uint32_t)(q0 - o);
-            pa = (uint32_t)head[0] + (uint32_t)pre[0];
-            pa2 = (uint32_t)head[1] + (uint32_t)pre[1] + d * (uint32_t)pre[0];
-            pb = (uint32_t)head[2] + (uint32_t)pre[2];
-            pb2 = (uint32_t)head[3] + (uint32_t)pre[3] + d * (uint32_t)pre[2];
-        } else {
-            const int32_t* L = s_seg[kb - kb0];
-            const uint32_t d = (uint32_t)(o - q0);
-            pa = (uint32_t)(pre[0] - L[0]);
-            pa2 = (uint32_t)(pre[1] - L[1]) - d * pa;
-            pb = (uint32_t)(pre[2] - L[2]);
-            pb2 = (uint32_t)(pre[3] - L[3]) - d * pb;
-        }
-        const uint32_t s1o = (uint32_t)To & 0xFFFFu, s2o = (uint32_t)To >> 16;
-        const uint32_t P1e = s1o + pb;
-        const uint32_t P2e = (uint32_t)B * s1o - s2o + pb2;
-        uint32_t u1 = P1e - pa;
-        uint32_t u2 = (uint32_t)(p0 + B - o) * u1 - (P2e - pa2);
+        uint32_t u1, u2;
+        chain_tile_start(K, q0, F.B, L.seg, u1, u2);
         uint32_t bits = 0;
 #pragma unroll 1
         for (int hh = 0; hh < 2; ++hh) {
-            uint32_t wa[4], wb[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                wa[j] = hh ? xa[1][j] : xa[0][j];
-                wb[j] = hh ? xb[1][j] : xb[0][j];
-            }
             uint32_t keys[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                keys[i] = (u1 & 0xFFFFu) | (u2 << 16);
-                const int32_t xo = sbyte_of(wa, i), xi = sbyte_of(wb, i);
-                u1 += (uint32_t)(xi - xo);
-                u2 += u1 - (uint32_t)__mul24((int)B, xo);  // (B <= 2^17: a full-rate 24-bit multiply)
-            }
-            bits |= chain_mask16(kset, keys) << (16 * hh);
+            chain_tile_half(K, hh, F.B, u1, u2, keys);
+            bits |= chain_mask16(L.kset, keys) << (16 * hh);
         }
         if (hend - p0 < 32) bits &= (1u << (uint32_t)(hend - p0)) - 1u;  // windows past hend: not searched
         __hip_atomic_store(&F.hmap[p0 >> 5], ((unsigned long long)gen << 32) | bits, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
-    __syncthreads();  // (s_seg and sh: the next tile)
+    __syncthreads();  // (seg and sh: the next tile)
+}
+
+// The first unset chain flag in [k, nflags), or nflags (all threads; zero: one LDS word).  One aligned 16-byte line of
+// flags per lane per pass: an identical file's 16384 flags in two passes instead of 32 load-and-barrier rounds.  A
+// line may start before flag k (or before the file's flags, inside the batch's flag buffer) and is masked to
+// [k, nflags); a line past the end is read bytewise.  EARLY: a barrier and a test after every pass, so the scan stops
+// at the first pass with an unset flag; else all passes, then one barrier.
+template <bool EARLY>
+__device__ __forceinline__ int64_t chain_first_unset_flag(const uint8_t* __restrict__ flags, int64_t k, int64_t nflags,
+                                                          int64_t* zero) {
+    const int t = threadIdx.x;
+    if (t == 0) *zero = nflags;
+    __syncthreads();
+    const uintptr_t fa = reinterpret_cast<uintptr_t>(flags);
+    for (uintptr_t l0 = (fa + (uintptr_t)k) & ~(uintptr_t)15; l0 < fa + (uintptr_t)nflags; l0 += 16u * CHAIN_THREADS) {
+        const uintptr_t la = l0 + 16u * (uintptr_t)t;
+        const int64_t jb = (int64_t)la - (int64_t)fa;  // flag index of the line's first byte
+        int64_t z = -1;
+        if (la < fa + (uintptr_t)nflags) {
+            uint32_t w[4] = {0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};
+            if (la + 16 <= fa + (uintptr_t)nflags) {
+                const uint4 q = *reinterpret_cast<const uint4*>(la);
+                w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
+            } else {
+                for (int i = 0; i < 16; ++i)
+                    if (jb + i >= 0 && jb + i < nflags && flags[jb + i] == 0) w[i >> 2] &= ~(0xFFu << (8 * (i & 3)));
+            }
+#pragma unroll
+            for (int i = 15; i >= 0; --i)
+                if (jb + i >= k && jb + i < nflags && ((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) == 0u) z = jb + i;
+        }
+        if (z >= 0) atomicMin((unsigned long long*)zero, (unsigned long long)z);
+        if (EARLY) {
+            __syncthreads();
+            if (*zero < nflags) break;
+        }
+    }
+    if (!EARLY) __syncthreads();
+    const int64_t first = *zero;
+    __syncthreads();
+    return first;
+}
+
+// Narrow blocks (B not a multiple of CHAIN_PPT, or < 512): the walk's search of [a, stop] in tiles of PROBE_TILE
+// positions in block coordinates, each lane anchored on its block's T(o).  The first hit's position and key in p, key
+// (p stays -1 without one); returns true when the search reached windows past the speculation (block >= na).
+__device__ __forceinline__ bool chain_narrow_search(const ChainFile& F, int64_t a, int64_t stop, int64_t na,
+                                                    const ChainLds& L, int32_t& tiles, int64_t& p, uint32_t& key) {
+    const int t = threadIdx.x;
+    const int64_t n = F.n, B = F.B;
+    for (int64_t q0 = (a / B) * B + ((a % B) / PROBE_TILE) * PROBE_TILE; p < 0 && q0 <= stop;) {
+        const int64_t kb = q0 / B, o = kb * B;
+        if (kb >= na) return true;
+        int64_t qend = q0 + PROBE_TILE;
+        if (qend > o + B) qend = o + B;
+        ++tiles;
+        int32_t head[4] = {0, 0, 0, 0};
+        if (q0 > o) {  // prefix of both streams from the block origin up to the tile
+            range_sums(F.data, n, o, q0, o, head[0], head[1]);
+            range_sums(F.data, n, o + B, q0 + B, o, head[2], head[3]);
+            block_reduce<4>(head, L.sh);
+        }
+        const int64_t p0 = q0 + (int64_t)t * PROBE_PPT;
+        uint32_t xa[4], xb[4];
+        load16(F.data, n, p0, xa);
+        load16(F.data, n, p0 + B, xb);
+        int32_t part[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < PROBE_PPT; ++i) {
+            const int32_t va = sbyte_of(xa, i), vb = sbyte_of(xb, i);
+            part[0] += va;
+            part[1] += (int32_t)((uint32_t)(p0 + i - o) * (uint32_t)va);
+            part[2] += vb;
+            part[3] += (int32_t)((uint32_t)(p0 + B + i - o) * (uint32_t)vb);
+        }
+        int32_t pre[4] = {part[0], part[1], part[2], part[3]};
+        block_exscan<4>(pre, L.sh);
+        if (t == 0) *L.hit = 0x7FFFFFFF;
+        __syncthreads();
+        uint32_t keys[PROBE_PPT];
+        if (t < PROBE_THREADS && p0 < qend && p0 <= stop && p0 + PROBE_PPT > a) {
+            const uint32_t pa = (uint32_t)(head[0] + pre[0]), pa2 = (uint32_t)(head[1] + pre[1]);
+            const uint32_t pb = (uint32_t)(head[2] + pre[2]), pb2 = (uint32_t)(head[3] + pre[3]);
+            const int32_t To = F.aw[kb];
+            const uint32_t s1o = (uint32_t)To & 0xFFFFu, s2o = (uint32_t)To >> 16;
+            const uint32_t P1e = s1o + pb;
+            const uint32_t P2e = (uint32_t)B * s1o - s2o + pb2;  // windows inside [o, nB]: e0 = o + B
+            const uint32_t s1 = P1e - pa;
+            const uint32_t s2 = (uint32_t)(p0 + B - o) * s1 - (P2e - pa2);  // (p0 + B - o) s1 - sum (j - o) x_j
+            int32_t R = (int32_t)((s1 & 0xFFFFu) | (s2 << 16));  // synced: the key is the true weak sum
+#pragma unroll
+            for (int i = 0; i < PROBE_PPT; ++i) {
+                keys[i] = (uint32_t)R;
+                R = roll_add(roll_sub(R, (int32_t)B, sbyte_of(xa, i)), sbyte_of(xb, i));
+            }
+            uint32_t valid = 0;
+#pragma unroll
+            for (int i = 0; i < PROBE_PPT; ++i) {
+                const int64_t pp = p0 + i;
+                if (pp >= a && pp <= stop && pp < qend) valid |= 1u << i;
+            }
+            const int h = chain_first_hit16(F.kslots, F.kmask, L.kset, keys, valid);
+            if (h >= 0) atomicMin(L.hit, (int32_t)(p0 + h - q0));
+        }
+        __syncthreads();
+        const int32_t hoff = *L.hit;
+        if (hoff != 0x7FFFFFFF && (hoff >> 4) == t) {
+#pragma unroll
+            for (int i = 0; i < PROBE_PPT; ++i)  // (a static index: keys stays in registers)
+                if (i == (hoff & 15)) *L.key = keys[i];
+        }
+        __syncthreads();
+        if (hoff != 0x7FFFFFFF) {
+            p = q0 + hoff;
+            key = *L.key;
+        }
+        __syncthreads();
+        q0 = qend;
+    }
+    return false;
+}
+
+// An event's bucket: the chunks with this key, in L.bk in ascending chunk index (Multimap order), their count in
+// L.nbk (it may exceed CHAIN_BUCKET_CAP: the walk then stops).  Every chunk with the key lies on its probe path before
+// the first empty slot: wave 0 reads 64 slots of it per round trip (one, nearly always) instead of one dependent load
+// per slot.  (all threads call it; the caller's barrier follows)
+__device__ __forceinline__ void chain_bucket_gather(const ChainFile& F, uint32_t key, const ChainLds& L) {
+    const int t = threadIdx.x;
+    if (t >= 64) return;
+    int32_t cnt = 0;
+    const unsigned long long* ks = F.kslots;
+    uint32_t h = slot_hash(key) & F.kmask;
+    for (bool more = true; more; h = (h + 64u) & F.kmask) {
+        const unsigned long long v = ks[(h + (uint32_t)t) & F.kmask];
+        const unsigned long long empty = __ballot(v == 0ull);
+        const int lim = empty ? __builtin_ctzll(empty) : 64;  // slots before the first empty one
+        const bool mine = t < lim && (uint32_t)(v >> 32) == key;
+        const unsigned long long hits = __ballot(mine);
+        const int at = cnt + __popcll(hits & ((1ull << t) - 1ull));
+        if (mine && at < CHAIN_BUCKET_CAP) L.bk[at] = (int32_t)((uint32_t)v - 1u);
+        cnt += __popcll(hits);
+        more = empty == 0ull;
+    }
+    if (t == 0) {  // ascending chunk index (insertion order); the wave's LDS operations execute in order
+        *L.nbk = cnt;
+        for (int i = 1; i < cnt && i < CHAIN_BUCKET_CAP; ++i)
+            for (int j = i; j > 0 && L.bk[j - 1] > L.bk[j]; --j) {
+                const int32_t x = L.bk[j];
+                L.bk[j] = L.bk[j - 1];
+                L.bk[j - 1] = x;
+            }
+    }
+}
+// closeIndexOf(bucket, pref) (Checksum.java:175-213): pref's position in the bucket, else that of the first index
+// above it, else the last; not length-filtered
+__device__ __forceinline__ int32_t chain_close_index(const int32_t* bk, int32_t size, int32_t pref) {
+    int32_t l = 0, r = size - 1;
+    while (l <= r) {
+        const int32_t mid = l + (r - l) / 2;
+        if (bk[mid] == pref) return mid;
+        if (bk[mid] < pref) l = mid + 1;
+        else r = mid - 1;
+    }
+    return l < size - 1 ? l : size - 1;
+}
+
+// What a walk only adds up and hands back: the file's totals (ChainOut carries them from phase 0 to phase 1) and
+// this launch's section timers (added to ChainOut's)
+struct ChainTally {
+    int64_t lit, mat, chain_matches, events, flushes;
+    int32_t tiles, digests, mapped, first_mapped;
+    int64_t t_tiles, t_check, t_event, t_digest, t_kset, t_chain, t_drain, t_evb;
+};
+// The walk's record for the host (lane 0, after the events are drained): the state it stopped in, why, the tally;
+// stale: the cached digest of a poisoned state, else null; fin last, after a system-scope fence
+__device__ __forceinline__ void chain_write_out(const ChainFile& F, int phase, int abort_gen, int64_t s, int64_t m,
+                                                int32_t pref, int32_t nev, int32_t status, int32_t why,
+                                                int64_t clear_to, uint32_t elo, uint32_t ehi, const uint8_t* stale,
+                                                bool dead, const ChainTally& N, int64_t t_total) {
+    ChainOut* out = F.out;
+    out->s = s;
+    out->m = m;
+    out->pref = pref;
+    out->status = status;
+    out->n_ev = nev;
+    out->tiles = N.tiles;
+    out->digests = N.digests;
+    out->flushes = N.flushes;
+    out->t_total += t_total;
+    out->t_tiles += N.t_tiles;
+    out->t_check += N.t_check;
+    out->t_event += N.t_event;
+    out->t_digest += N.t_digest;
+    out->t_kset += N.t_kset;
+    out->t_chain += N.t_chain;
+    out->t_drain += N.t_drain;
+    out->t_evb += N.t_evb;
+    out->spec_full = phase == 1;
+    out->mapped = N.mapped;
+    out->clear_to = clear_to;
+    out->why = why;
+    out->elo = elo;
+    out->ehi = ehi;
+    out->first_mapped = N.first_mapped;
+    // a file that needs no more speculation stops its phase-1 K1 groups (they poll this word); any other stop
+    // keeps them (the resolver's aligned lookups past the prefix use them)
+    const bool stop_spec = phase == 0 && F.abort && (status == CHAIN_DONE || dead);
+    out->aborted = stop_spec;
+    if (stop_spec) *(volatile int*)F.abort = abort_gen;
+    out->md5c_valid = stale != nullptr;
+    if (stale != nullptr)
+        for (int j = 0; j < F.dl && j < 16; ++j) out->md5c[j] = stale[j];
+    out->literal = N.lit;
+    out->matched = N.mat;
+    out->chain_matches = N.chain_matches;
+    out->events = N.events;
+    __threadfence_system();  // the record and the events (drained above) before the completion word
+    *(volatile int32_t*)&out->fin = 1;
 }
 
 constexpr int CHAIN_HELP_LEAD = 64;   // a helper stays with its file while the map leads the walk by fewer segments
@@ -387,17 +650,14 @@ constexpr int CHAIN_HELP_LEAD = 64;   // a helper stays with its file while the 
 // a map word only when it carries this launch's generation, and searches the tile itself otherwise.  (A helper waits
 // only for walks of its own launch, whose workgroups precede it in dispatch order.)
 __device__ __attribute__((noinline)) void chain_help(const ChainFile* __restrict__ files, int nfiles, uint32_t gen,
-                                                     ChainHelp* help, uint2* ck, int32_t* ck_full,
-                                                     int32_t* sh, int32_t (*s_seg)[4], unsigned long long* s_best,
-                                                     int32_t* s_word, int32_t* s_live, bool timed) {
+                                                     ChainHelp* help, const ChainLds L, bool timed) {
     const int t = threadIdx.x;
-    const ChainKeySet kset{ck, ck_full};
     int cur = -1;
     ChainFile F = files[0];
     for (;;) {
         if (t == 0) {
-            *s_best = 0ull;
-            *s_live = 0;
+            *L.best = 0ull;
+            *L.live = 0;
         }
         __syncthreads();
         for (int f = t; f < nfiles; f += CHAIN_THREADS) {
@@ -409,7 +669,7 @@ __device__ __attribute__((noinline)) void chain_help(const ChainFile* __restrict
             const int32_t nhelp = chain_ld(&h->nhelp);
             const int64_t pos = chain_ld64(&h->pos);
             if (live == 0 || claim >= nseg) continue;
-            *s_live = 1;  // a walk that may still search: wait for it rather than leave
+            *L.live = 1;  // a walk that may still search: wait for it rather than leave
             if (tiles < h->help_tiles) continue;
             // the most urgent files first -- the map's frontier least far ahead of the walk, in four levels -- then
             // the fewest helpers, then a hash that spreads the helpers; the current file while the map leads its
@@ -421,11 +681,11 @@ __device__ __attribute__((noinline)) void chain_help(const ChainFile* __restrict
             const unsigned long long key = ((unsigned long long)(f == cur && lead < CHAIN_HELP_LEAD) << 63) |
                                            ((unsigned long long)level << 61) | ((unsigned long long)few << 53) |
                                            ((unsigned long long)(tie >> 1) << 21) | (uint32_t)f;
-            atomicMax(s_best, key);
+            atomicMax(L.best, key);
         }
         __syncthreads();
-        const unsigned long long best = *s_best;
-        const bool any_live = *s_live != 0;
+        const unsigned long long best = *L.best;
+        const bool any_live = *L.live != 0;
         __syncthreads();
         if (best == 0ull) {
             if (!any_live) break;  // every mappable walk has ended: nothing will come
@@ -436,10 +696,10 @@ __device__ __attribute__((noinline)) void chain_help(const ChainFile* __restrict
         ChainHelp* h = help + f;
         if (t == 0) {  // the segment the walk is in and those behind it are skipped, not claimed one by one
             atomicMax(&h->claim, (int32_t)(chain_ld64(&h->pos) / CHAIN_MAP_SEG) + 1);
-            *s_word = atomicAdd(&h->claim, 1);
+            *L.word = atomicAdd(&h->claim, 1);
         }
         __syncthreads();
-        const int32_t seg = *s_word;
+        const int32_t seg = *L.word;
         __syncthreads();
         if (seg >= h->nseg) continue;
         if (f != cur) {
@@ -450,12 +710,12 @@ __device__ __attribute__((noinline)) void chain_help(const ChainFile* __restrict
             cur = f;
             const int64_t tb = chain_clock(timed);
             F = files[f];
-            chain_kset_build(kset, F.table_weak, F.C);
+            chain_kset_build(L.kset, F.table_weak, F.C);
             if (t == 0) {
                 atomicAdd((unsigned long long*)&h->t_kset, (unsigned long long)(chain_clock(timed) - tb));
                 atomicAdd(&h->joins, 1);
             }
-            if (*kset.full) {  // not exact: the walk confirms keys in the chunk index; no map for this file
+            if (*L.kset.full) {  // not exact: the walk confirms keys in the chunk index; no map for this file
                 if (t == 0) atomicMax(&h->claim, h->nseg);
                 __syncthreads();
                 continue;
@@ -464,15 +724,15 @@ __device__ __attribute__((noinline)) void chain_help(const ChainFile* __restrict
         const int64_t lo = (int64_t)seg * CHAIN_MAP_SEG, hi = lo + CHAIN_MAP_SEG < F.hend ? lo + CHAIN_MAP_SEG : F.hend;
         bool whole = true;
         for (int64_t q0 = lo; q0 < hi; q0 += CHAIN_TILE) {
-            if (t == 0) *s_word = chain_ld(&h->live) != 0 && chain_ld64(&h->pos) < q0 + CHAIN_TILE;
+            if (t == 0) *L.word = chain_ld(&h->live) != 0 && chain_ld64(&h->pos) < q0 + CHAIN_TILE;
             __syncthreads();
-            const bool go = *s_word != 0;
+            const bool go = *L.word != 0;
             __syncthreads();
             if (!go) {
                 whole = false;
                 break;
             }
-            chain_map_tile(F, q0, gen, kset, sh, s_seg);
+            chain_map_tile(F, q0, gen, L);
         }
         if (t == 0) {
             atomicAdd(&h->mapped, 1);
@@ -506,9 +766,11 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
     __shared__ unsigned long long s_best;      // helpers: the file to map next
     __shared__ int32_t s_word, s_live;
     const ChainKeySet kset{s_ck, &s_ck_full};
+    ChainLds L;  // (member by member: an aggregate of LDS addresses is no constant initializer)
+    L.kset = kset, L.sh = sh, L.seg = s_seg, L.hit = &s_hit, L.key = &s_key, L.bk = s_bk, L.nbk = &s_nbk;
+    L.zero = &s_zero, L.best = &s_best, L.word = &s_word, L.live = &s_live;
     if ((int)blockIdx.x >= nfiles) {  // a helper workgroup (phase 0): it only maps
-        chain_help(files, nfiles, (uint32_t)abort_gen, help, s_ck, &s_ck_full, sh, s_seg, &s_best, &s_word, &s_live,
-                   timed != 0);
+        chain_help(files, nfiles, (uint32_t)abort_gen, help, L, timed != 0);
         return;
     }
     // the descriptor by value: it sits in pinned host memory, and a reference would let the compiler re-read its
@@ -532,47 +794,16 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
     // an unbroken run of chain flags up to the last window with a chunk (an identical file, or its rest after the
     // prefix) follows the chain and never looks a key up; should it need one after all, it stops there (the host).
     bool kset_built = true;
-    if (s % B == 0 && nflags >= na) {
-        if (t == 0) s_zero = nflags;
-        __syncthreads();
-        // one 16-byte line of flags per lane per pass (as in step (1) below), masked to [s / B, nflags)
-        const int64_t k = s / B;
-        const uintptr_t fa = reinterpret_cast<uintptr_t>(F.flags);
-        for (uintptr_t l0 = (fa + (uintptr_t)k) & ~(uintptr_t)15; l0 < fa + (uintptr_t)nflags;
-             l0 += 16u * CHAIN_THREADS) {
-            const uintptr_t la = l0 + 16u * (uintptr_t)t;
-            const int64_t jb = (int64_t)la - (int64_t)fa;
-            if (la < fa + (uintptr_t)nflags) {
-                uint32_t w[4] = {0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};
-                if (la + 16 <= fa + (uintptr_t)nflags) {
-                    const uint4 q = *reinterpret_cast<const uint4*>(la);
-                    w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
-                } else {
-                    for (int i = 0; i < 16; ++i)
-                        if (jb + i >= 0 && jb + i < nflags && F.flags[jb + i] == 0) w[i >> 2] &= ~(0xFFu << (8 * (i & 3)));
-                }
-                int64_t z = -1;
-#pragma unroll
-                for (int i = 15; i >= 0; --i)
-                    if (jb + i >= k && jb + i < nflags && ((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) == 0u) z = jb + i;
-                if (z >= 0) atomicMin((unsigned long long*)&s_zero, (unsigned long long)z);
-            }
-        }
-        __syncthreads();
-        kset_built = s_zero < nflags;  // (uniform) a break in the chain: the walk will search
-        __syncthreads();
-    }
+    if (s % B == 0 && nflags >= na)  // (uniform) a break in the chain: the walk will search
+        kset_built = chain_first_unset_flag<false>(F.flags, s / B, nflags, &s_zero) < nflags;
     const int64_t tks0 = chain_clock(timed);
     if (kset_built) chain_kset_build(kset, F.table_weak, C);
-    const int64_t t_kset = chain_clock(timed) - tks0;
+    ChainTally N{out->literal, out->matched, out->chain_matches, out->events, out->flushes, out->tiles, out->digests,
+                 out->mapped, out->first_mapped, 0, 0, 0, 0, chain_clock(timed) - tks0, 0, 0, 0};
     int32_t pref = out->pref;
     int32_t nev = out->n_ev, status = CHAIN_STOP;
-    int64_t lit = out->literal, mat = out->matched, chain_matches = out->chain_matches, events = out->events;
-    int32_t tiles = out->tiles, digests = out->digests, poisoned = 0, dead = 0, mapped = out->mapped;
-    int32_t first_mapped = out->first_mapped;
-    int64_t flushes = out->flushes;
+    int32_t poisoned = 0, dead = 0;
     const int64_t tk0 = chain_clock(timed);
-    int64_t t_tiles = 0, t_check = 0, t_event = 0, t_digest = 0, t_chain = 0, t_drain = 0, t_evb = 0;
     const uint8_t* stale = nullptr;  // poisoned: the cached digest
     uint32_t dg[4] = {0u, 0u, 0u, 0u};  // the window's digest at the current event (poisoned: the stale one)
     int64_t clear_to = -1;            // stopped at a flush point: no candidate in [s, clear_to]
@@ -599,7 +830,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
         for (int32_t i = t; i < nev - nev_w; i += CHAIN_THREADS) F.ev[nev_w + i] = s_ev[i];
         nev_w = nev;
         __syncthreads();
-        t_drain += chain_clock(timed) - tdr0;
+        N.t_drain += chain_clock(timed) - tdr0;
     };
     auto flush_pend = [&]() {  // (the loop drains at its top while fewer than CHAIN_EV_LDS - 8 are held)
         if (have) {
@@ -613,10 +844,10 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
         flush_pend();
         pend = rsh_event{off, len, RSH_EV_LITERAL, 0, 0, 0};
         have = true;
-        lit += len;
+        N.lit += len;
     };
     auto emit_match = [&](int64_t off, int64_t len, int32_t idx, int32_t cnt) {
-        mat += len;
+        N.mat += len;
         if (have && pend.kind == RSH_EV_MATCH && pend.index + pend.count == idx && pend.offset + pend.length == off) {
             pend.count += cnt;
             pend.length += len;
@@ -659,45 +890,16 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
         // (1) aligned chain: preferred index == k and source window k carries chunk k's sums
         const int64_t tch0 = chain_clock(timed);
         if (flag_k) {
-            if (t == 0) s_zero = nflags;
-            __syncthreads();
-            // one aligned 16-byte line of flags per lane per pass: an identical file's 16384 flags in two passes
-            // instead of 32 load-and-barrier rounds.  A line may start before flag k (or before the file's flags,
-            // inside the batch's flag buffer) and is masked to [k, nflags); a line past the end is read bytewise.
-            const uintptr_t fa = reinterpret_cast<uintptr_t>(F.flags);
-            for (uintptr_t l0 = (fa + (uintptr_t)k) & ~(uintptr_t)15; l0 < fa + (uintptr_t)nflags;
-                 l0 += 16u * CHAIN_THREADS) {
-                const uintptr_t la = l0 + 16u * (uintptr_t)t;
-                const int64_t jb = (int64_t)la - (int64_t)fa;  // flag index of the line's first byte
-                int64_t z = -1;
-                if (la < fa + (uintptr_t)nflags) {
-                    uint32_t w[4] = {0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};
-                    if (la + 16 <= fa + (uintptr_t)nflags) {
-                        const uint4 q = *reinterpret_cast<const uint4*>(la);
-                        w[0] = q.x, w[1] = q.y, w[2] = q.z, w[3] = q.w;
-                    } else {
-                        for (int i = 0; i < 16; ++i)
-                            if (jb + i >= 0 && jb + i < nflags && F.flags[jb + i] == 0) w[i >> 2] &= ~(0xFFu << (8 * (i & 3)));
-                    }
-#pragma unroll
-                    for (int i = 15; i >= 0; --i)
-                        if (jb + i >= k && jb + i < nflags && ((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) == 0u) z = jb + i;
-                }
-                if (z >= 0) atomicMin((unsigned long long*)&s_zero, (unsigned long long)z);
-                __syncthreads();
-                if (s_zero < nflags) break;
-            }
-            const int64_t j_end = s_zero;
-            __syncthreads();
+            const int64_t j_end = chain_first_unset_flag<true>(F.flags, k, nflags, &s_zero);
             const int64_t t_max = (last - s) / B + 1;
             const int64_t tt = (j_end - k < t_max) ? j_end - k : t_max;
             const int64_t j = k + tt, p = (s + tt * B < n) ? s + tt * B : n;
             emit_lit(m, s - m);
             emit_match(s, p - s, (int32_t)k, (int32_t)(j - k));
-            chain_matches += j - k;
+            N.chain_matches += j - k;
             s = m = p;
             pref = (int32_t)j;
-            t_chain += chain_clock(timed) - tch0;
+            N.t_chain += chain_clock(timed) - tch0;
             continue;
         }
         // (1') the window at s against chunk pref while both sums agree (windows s + iB, chunks pref + i)
@@ -718,11 +920,11 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
                 emit_match(s, p - s, pref, (int32_t)tt);
                 s = m = p;
                 pref += (int32_t)tt;
-                t_chain += chain_clock(timed) - tch0;
+                N.t_chain += chain_clock(timed) - tch0;
                 continue;
             }
         }
-        t_chain += chain_clock(timed) - tch0;
+        N.t_chain += chain_clock(timed) - tch0;
         // (2) the next candidate event in [s, stop]
         const int64_t f = (m + 10 * B <= n) ? m + 9 * B : INT64_MAX;
         const int64_t stop = f < last ? f : last;
@@ -747,18 +949,16 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
         bool sc_hit = false;  // the hit came from the map at an aligned window: s_sc holds its chunk's words
         bool cut = false;  // the search reached windows past the speculation (no anchor T(o))
         if (wide) {
-            // tiles of CHAIN_TILE positions from a (lane-aligned), across block boundaries: each lane anchors its
-            // 16 positions on its own block's T(o); the prefix sums from o come from one exscan over the tile
-            // with weights relative to the tile start, rebased at each block's first lane (a segmented scan), and
-            // the head of the block the tile starts in (range_sums from o to the tile)
+            // tiles of CHAIN_TILE positions from a (lane-aligned), across block boundaries: from the hit map where a
+            // helper has been, else searched here with the lanes' keys (ChainTileKeys)
             const int64_t lim_spec = na * B - 1;  // windows with an anchor: blocks < na
             const int64_t qlast = stop < lim_spec ? stop : lim_spec;
             if (H != nullptr && t == 0) {  // for the helpers: where this search starts, how many tiles so far
                 chain_st64(&H->pos, a);
-                chain_st(&H->tiles, tiles);
+                chain_st(&H->tiles, N.tiles);
             }
             for (int64_t q0 = a & ~(int64_t)(CHAIN_PPT - 1); p < 0 && q0 <= qlast;) {
-                ++tiles;
+                ++N.tiles;
                 const int64_t tt0 = chain_clock(timed);
                 if (map_gen != 0u) {
                     // the tile from the hit map when every word it needs carries this launch's generation: lane t's
@@ -810,82 +1010,31 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
                                 key = (S1 & 0xFFFFu) | (S2 << 16);
                             }
                         }
-                        if (mapped++ == 0) first_mapped = tiles;
+                        if (N.mapped++ == 0) N.first_mapped = N.tiles;
                         q0 += CHAIN_TILE;
-                        t_tiles += chain_clock(timed) - tt0;
+                        N.t_tiles += chain_clock(timed) - tt0;
                         continue;
                     }
                 }
-                const int64_t kb0 = q0 / B, o0 = kb0 * B;
-                int32_t head[4] = {0, 0, 0, 0};
-                if (q0 > o0) {
-                    range_sums(F.data, n, o0, q0, o0, head[0], head[1]);
-                    range_sums(F.data, n, o0 + B, q0 + B, o0, head[2], head[3]);
-                    block_reduce<4>(head, sh);
-                }
+                // the lane's keys: the derivation chain_map_tile shares
                 const int64_t p0 = q0 + (int64_t)t * CHAIN_PPT;
-                const int64_t kb = p0 / B, o = kb * B;
-                uint32_t xa[2][4], xb[2][4];
-                load16(F.data, n, p0, xa[0]);
-                load16(F.data, n, p0 + 16, xa[1]);
-                load16(F.data, n, p0 + B, xb[0]);
-                load16(F.data, n, p0 + B + 16, xb[1]);
                 const bool live = p0 <= stop && p0 <= lim_spec && p0 + CHAIN_PPT > a;
-                const int32_t To = live ? F.aw[kb] : 0;
-                int32_t pre[4];
-                chain_lane_sums(xa, xb, (uint32_t)(p0 - q0), (uint32_t)B, pre);
-                block_exscan<4>(pre, sh);  // sums over [q0, p0) and [q0 + B, p0 + B), weights j - q0
-                if (p0 == o) {              // a block's first lane: its rebasing point
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) s_seg[kb - kb0][v] = pre[v];
-                }
+                ChainTileKeys K;
+                chain_tile_sums(K, F, q0, live, L);
                 if (t == 0) s_hit = 0x7FFFFFFF;
                 __syncthreads();
                 const int64_t tc0 = chain_clock(timed);
                 int32_t my_hit = 0x7FFFFFFF;
                 uint32_t my_key = 0;
                 if (live) {
-                    uint32_t pa, pa2, pb, pb2;  // sums over [o, p0) and [o + B, p0 + B), weights j - o
-                    if (o < q0) {               // the tile's first block: its head + the tile's part
-                        const uint32_t d = (uint32_t)(q0 - o);
-                        pa = (uint32_t)head[0] + (uint32_t)pre[0];
-                        pa2 = (uint32_t)head[1] + (uint32_t)pre[1] + d * (uint32_t)pre[0];
-                        pb = (uint32_t)head[2] + (uint32_t)pre[2];
-                        pb2 = (uint32_t)head[3] + (uint32_t)pre[3] + d * (uint32_t)pre[2];
-                    } else {                    // rebased at the block's first lane
-                        const int32_t* L = s_seg[kb - kb0];
-                        const uint32_t d = (uint32_t)(o - q0);
-                        pa = (uint32_t)(pre[0] - L[0]);
-                        pa2 = (uint32_t)(pre[1] - L[1]) - d * pa;
-                        pb = (uint32_t)(pre[2] - L[2]);
-                        pb2 = (uint32_t)(pre[3] - L[3]) - d * pb;
-                    }
-                    const uint32_t s1o = (uint32_t)To & 0xFFFFu, s2o = (uint32_t)To >> 16;
-                    const uint32_t P1e = s1o + pb;
-                    const uint32_t P2e = (uint32_t)B * s1o - s2o + pb2;
-                    const uint32_t s1 = P1e - pa;
-                    const uint32_t s2 = (uint32_t)(p0 + B - o) * s1 - (P2e - pa2);
-                    // the lane's 32 positions as two halves of 16 (the first hit of the first half wins).  The two
-                    // 16-bit halves of the rolling value are kept apart (u1, u2: each exact mod 2^16, the Java
-                    // subtract-then-add of Rolling.java:25-60 in two adds each), packed into the key per position
-                    uint32_t u1 = s1, u2 = s2;
+                    // the lane's 32 positions as two halves of 16 (the first hit of the first half wins)
+                    uint32_t u1, u2;
+                    chain_tile_start(K, q0, (uint32_t)B, L.seg, u1, u2);
                     const int64_t lim_p = stop < lim_spec ? stop : lim_spec;
 #pragma unroll 1
                     for (int hh = 0; hh < 2; ++hh) {  // (not unrolled: one half's keys in registers at a time)
-                        uint32_t wa[4], wb[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            wa[j] = hh ? xa[1][j] : xa[0][j];
-                            wb[j] = hh ? xb[1][j] : xb[0][j];
-                        }
                         uint32_t keys[16];
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            keys[i] = (u1 & 0xFFFFu) | (u2 << 16);
-                            const int32_t xo = sbyte_of(wa, i), xi = sbyte_of(wb, i);
-                            u1 += (uint32_t)(xi - xo);
-                            u2 += u1 - (uint32_t)__mul24((int)B, xo);  // (B <= 2^17: a full-rate 24-bit multiply)
-                        }
+                        chain_tile_half(K, hh, (uint32_t)B, u1, u2, keys);
                         // positions base + i with a <= position <= lim_p, as a bit range
                         const int64_t base = p0 + 16 * hh;
                         const int64_t lo = a > base ? a - base : 0, hi = lim_p - base;
@@ -905,7 +1054,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
                     if (my_hit != 0x7FFFFFFF) atomicMin(&s_hit, my_hit);
                 }
                 __syncthreads();
-                t_check += chain_clock(timed) - tc0;
+                N.t_check += chain_clock(timed) - tc0;
                 if (my_hit != 0x7FFFFFFF && my_hit == s_hit) s_key = my_key;
                 __syncthreads();
                 if (s_hit != 0x7FFFFFFF) {
@@ -914,82 +1063,11 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
                 }
                 __syncthreads();
                 q0 += CHAIN_TILE;
-                t_tiles += chain_clock(timed) - tt0;
+                N.t_tiles += chain_clock(timed) - tt0;
             }
             cut = p < 0 && stop > lim_spec;  // (lim_spec, stop] has no anchors: not searched
         }
-        // narrow blocks (B not a multiple of 16, or < 512): tiles of PROBE_TILE positions in block coordinates
-        for (int64_t q0 = (a / B) * B + ((a % B) / PROBE_TILE) * PROBE_TILE; !wide && p < 0 && q0 <= stop;) {
-            const int64_t kb = q0 / B, o = kb * B;
-            if (kb >= na) {
-                cut = true;
-                break;
-            }
-            int64_t qend = q0 + PROBE_TILE;
-            if (qend > o + B) qend = o + B;
-            ++tiles;
-            int32_t head[4] = {0, 0, 0, 0};
-            if (q0 > o) {  // prefix of both streams from the block origin up to the tile
-                range_sums(F.data, n, o, q0, o, head[0], head[1]);
-                range_sums(F.data, n, o + B, q0 + B, o, head[2], head[3]);
-                block_reduce<4>(head, sh);
-            }
-            const int64_t p0 = q0 + (int64_t)t * PROBE_PPT;
-            uint32_t xa[4], xb[4];
-            load16(F.data, n, p0, xa);
-            load16(F.data, n, p0 + B, xb);
-            int32_t part[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < PROBE_PPT; ++i) {
-                const int32_t va = sbyte_of(xa, i), vb = sbyte_of(xb, i);
-                part[0] += va;
-                part[1] += (int32_t)((uint32_t)(p0 + i - o) * (uint32_t)va);
-                part[2] += vb;
-                part[3] += (int32_t)((uint32_t)(p0 + B + i - o) * (uint32_t)vb);
-            }
-            int32_t pre[4] = {part[0], part[1], part[2], part[3]};
-            block_exscan<4>(pre, sh);
-            if (t == 0) s_hit = 0x7FFFFFFF;
-            __syncthreads();
-            uint32_t keys[PROBE_PPT];
-            if (t < PROBE_THREADS && p0 < qend && p0 <= stop && p0 + PROBE_PPT > a) {
-                const uint32_t pa = (uint32_t)(head[0] + pre[0]), pa2 = (uint32_t)(head[1] + pre[1]);
-                const uint32_t pb = (uint32_t)(head[2] + pre[2]), pb2 = (uint32_t)(head[3] + pre[3]);
-                const int32_t To = F.aw[kb];
-                const uint32_t s1o = (uint32_t)To & 0xFFFFu, s2o = (uint32_t)To >> 16;
-                const uint32_t P1e = s1o + pb;
-                const uint32_t P2e = (uint32_t)B * s1o - s2o + pb2;  // windows inside [o, nB]: e0 = o + B
-                const uint32_t s1 = P1e - pa;
-                const uint32_t s2 = (uint32_t)(p0 + B - o) * s1 - (P2e - pa2);  // (p0 + B - o) s1 - sum (j - o) x_j
-                int32_t R = (int32_t)((s1 & 0xFFFFu) | (s2 << 16));  // synced: the key is the true weak sum
-#pragma unroll
-                for (int i = 0; i < PROBE_PPT; ++i) {
-                    keys[i] = (uint32_t)R;
-                    R = roll_add(roll_sub(R, (int32_t)B, sbyte_of(xa, i)), sbyte_of(xb, i));
-                }
-                uint32_t valid = 0;
-#pragma unroll
-                for (int i = 0; i < PROBE_PPT; ++i) {
-                    const int64_t pp = p0 + i;
-                    if (pp >= a && pp <= stop && pp < qend) valid |= 1u << i;
-                }
-                const int h = chain_first_hit16(F.kslots, F.kmask, kset, keys, valid);
-                if (h >= 0) atomicMin(&s_hit, (int32_t)(p0 + h - q0));
-            }
-            __syncthreads();
-            if (s_hit != 0x7FFFFFFF && (s_hit >> 4) == t) {
-#pragma unroll
-                    for (int i = 0; i < PROBE_PPT; ++i)  // (a static index: keys stays in registers)
-                        if (i == (s_hit & 15)) s_key = keys[i];
-                }
-            __syncthreads();
-            if (s_hit != 0x7FFFFFFF) {
-                p = q0 + s_hit;
-                key = s_key;
-            }
-            __syncthreads();
-            q0 = qend;
-        }
+        if (!wide) cut = chain_narrow_search(F, a, stop, na, L, N.tiles, p, key);
         if (p < 0) {
             if (cut) {  // past the speculation: the rest of it (phase 1), or the host -- which also takes a
                 // poisoned walk (phase 1 starts from the unpoisoned state)
@@ -1010,7 +1088,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
         }
         // the event at p: its bucket (Multimap order), the candidates of Checksum.getCandidateChunks
         const int64_t te0 = chain_clock(timed);
-        ++events;
+        ++N.events;
         const int64_t kp = p / B;
         const bool spec_digest = !poisoned && p % B == 0 && kp < na;
         // An aligned hit on its own chunk (chain flag: the speculation's weak sum and digest are chunk kp's) whose weak
@@ -1028,7 +1106,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
             pref = (int32_t)(kp + 1);
             s = m = p + B;
             poisoned = 0;
-            t_event += chain_clock(timed) - te0;
+            N.t_event += chain_clock(timed) - te0;
             continue;
         }
         // the speculation's digest of an aligned window, loaded beside the bucket's slots (it depends only on p)
@@ -1046,53 +1124,16 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
             pf_aw = kn < na ? F.aw[kn] : 0;
             pf_tw = (kn < C && kn < na) ? F.table_weak[kn] : 0;
         }
-        if (t < 64) {
-            // every chunk with this key lies on the probe path before the first empty slot: wave 0 reads 64 slots of
-            // it per round trip (one, nearly always) instead of one dependent load per slot
-            int32_t cnt = 0;
-            const unsigned long long* ks = F.kslots;
-            uint32_t h = slot_hash(key) & F.kmask;
-            for (bool more = true; more; h = (h + 64u) & F.kmask) {
-                const unsigned long long v = ks[(h + (uint32_t)t) & F.kmask];
-                const unsigned long long empty = __ballot(v == 0ull);
-                const int lim = empty ? __builtin_ctzll(empty) : 64;  // slots before the first empty one
-                const bool mine = t < lim && (uint32_t)(v >> 32) == key;
-                const unsigned long long hits = __ballot(mine);
-                const int at = cnt + __popcll(hits & ((1ull << t) - 1ull));
-                if (mine && at < CHAIN_BUCKET_CAP) s_bk[at] = (int32_t)((uint32_t)v - 1u);
-                cnt += __popcll(hits);
-                more = empty == 0ull;
-            }
-            if (t == 0) {  // ascending chunk index (insertion order); the wave's LDS operations execute in order
-                s_nbk = cnt;
-                for (int i = 1; i < cnt && i < CHAIN_BUCKET_CAP; ++i)
-                    for (int j = i; j > 0 && s_bk[j - 1] > s_bk[j]; --j) {
-                        const int32_t x = s_bk[j];
-                        s_bk[j] = s_bk[j - 1];
-                        s_bk[j - 1] = x;
-                    }
-            }
-        }
+        chain_bucket_gather(F, key, L);
         __syncthreads();
-        t_evb += chain_clock(timed) - te0;
+        N.t_evb += chain_clock(timed) - te0;
         const int32_t size = s_nbk;
         if (size == 0 || size > CHAIN_BUCKET_CAP) {
             why = CHAIN_WHY_BUCKET;
             break;
         }
-        // closeIndexOf(bucket, pref) (Checksum.java:175-213): pref's position, else the first index above it,
-        // else the last; not length-filtered.  Then the others in ascending order with length == window.
-        int32_t l = 0, r = size - 1, init = -1;
-        while (l <= r) {
-            const int32_t mid = l + (r - l) / 2;
-            if (s_bk[mid] == pref) {
-                init = mid;
-                break;
-            }
-            if (s_bk[mid] < pref) l = mid + 1;
-            else r = mid - 1;
-        }
-        if (init < 0) init = l < size - 1 ? l : size - 1;
+        // the candidates: closeIndexOf(bucket, pref) first, then the others in ascending order with length == window
+        const int32_t init = chain_close_index(s_bk, size, pref);
         const int64_t w = B;  // p <= nB
         // Sender.java:1259-1263: the window's digest -- the speculation's at aligned positions, else one lane digests
         // the window here (lane_chunk_sums over the B bytes at p, the seed appended), the host path's md5_at
@@ -1102,8 +1143,8 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
             chain_window_digest(F.data + p, (uint32_t)B, (uint32_t)dl, F.seed, s_win, s_dig);  // (ends with a barrier)
             md5c = s_dig;
             chain_digest_load(s_dig, dl, dg);
-            ++digests;
-            t_digest += chain_clock(timed) - td0;
+            ++N.digests;
+            N.t_digest += chain_clock(timed) - td0;
         }
         int32_t hit = -1;
         for (int32_t it = -1; it < size && hit < 0; ++it) {
@@ -1122,7 +1163,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
             if (eq) hit = c;
         }
         __syncthreads();
-        t_event += chain_clock(timed) - te0;
+        N.t_event += chain_clock(timed) - te0;
         if (hit < 0) {
             // the cached digest is stale from here on (quirk B): the walk goes on with it from p + 1, comparing every
             // later candidate with it, up to the next flush point (a hit at the flush point itself flushes there: the
@@ -1158,9 +1199,9 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
                             F.ev[nev + i] = rsh_event{m + 10 * B * i, 10 * B, RSH_EV_LITERAL, 0, 0, 0};
                         nev += (int32_t)nfl;
                         nev_w = nev;
-                        lit += 10 * B * nfl;
+                        N.lit += 10 * B * nfl;
                         m += 10 * B * nfl;
-                        flushes += nfl;
+                        N.flushes += nfl;
                         emit_lit(m, n - m);
                         s = n;
                         status = CHAIN_DONE;
@@ -1180,7 +1221,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
                     stale = md5c;
                 }
                 emit_lit(m, p + B - m);
-                ++flushes;
+                ++N.flushes;
                 const int64_t s2 = p + B;
                 s = m = s2;
                 if (s2 <= last) {
@@ -1216,51 +1257,13 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_advance_kernel(const Chai
     }
     flush_pend();
     drain_ev();
-    if (t == 0) {
-        out->s = s;
-        out->m = m;
-        out->pref = pref;
-        out->status = status;
-        out->n_ev = nev;
-        out->tiles = tiles;
-        out->digests = digests;
-        out->flushes = flushes;
-        out->t_total += chain_clock(timed) - tk0;
-        out->t_tiles += t_tiles;
-        out->t_check += t_check;
-        out->t_event += t_event;
-        out->t_digest += t_digest;
-        out->t_kset += t_kset;
-        out->t_chain += t_chain;
-        out->t_drain += t_drain;
-        out->t_evb += t_evb;
-        out->spec_full = phase == 1;
-        out->mapped = mapped;
-        out->clear_to = clear_to;
-        out->why = why;
-        out->elo = desync_lo;
-        out->ehi = desync_hi;
-        out->first_mapped = first_mapped;
-        // a file that needs no more speculation stops its phase-1 K1 groups (they poll this word); any other stop
-        // keeps them (the resolver's aligned lookups past the prefix use them)
-        const bool stop_spec = phase == 0 && F.abort && (status == CHAIN_DONE || dead);
-        out->aborted = stop_spec;
-        if (stop_spec) *(volatile int*)F.abort = abort_gen;
-        out->md5c_valid = poisoned;
-        if (poisoned)
-            for (int j = 0; j < dl && j < 16; ++j) out->md5c[j] = stale[j];
-        out->literal = lit;
-        out->matched = mat;
-        out->chain_matches = chain_matches;
-        out->events = events;
-        __threadfence_system();  // the record and the events (drained above) before the completion word
-        *(volatile int32_t*)&out->fin = 1;
-    }
+    if (t == 0)
+        chain_write_out(F, phase, abort_gen, s, m, pref, nev, status, why, clear_to, desync_lo, desync_hi,
+                        poisoned ? stale : nullptr, dead != 0, N, chain_clock(timed) - tk0);
     if (H != nullptr) {  // this walk is over: its helpers stop, and the workgroup helps the walks still searching
         if (t == 0) chain_st(&H->live, 0);
         __syncthreads();
-        chain_help(files, nfiles, (uint32_t)abort_gen, help, s_ck, &s_ck_full, sh, s_seg, &s_best, &s_word, &s_live,
-                   timed != 0);
+        chain_help(files, nfiles, (uint32_t)abort_gen, help, L, timed != 0);
     }
 }
 
@@ -1329,11 +1332,13 @@ hipError_t launch_chunk_index(const ChunkIndexEnt* ents, uint32_t nfiles, int32_
 // A kernel that does nothing: its first launch makes the runtime load this file's code object (the chain walk) on a
 // fresh context, which rsh_ctx_create pays instead of the first segment scan (launch_warm).
 __global__ void warm_chain_kernel() {}
-// Scratch: chain_advance_kernel spills ~572 B per lane (256 VGPRs at two waves per SIMD) and its out-of-line helpers
-// keep their saved registers there.  The runtime sizes a queue's scratch at the first dispatch that needs it, which held
-// up the first segment scan's walk by ~0.7 ms; this kernel needs more per lane than the walk, over as many waves as a
-// walk launch can have (256 workgroups of 512), so rsh_ctx_create pays that instead (on the context stream, the walk's).
-constexpr int kWarmScratchWords = 160;  // 640 B per lane
+// Scratch: chain_advance_kernel spills registers (256 VGPRs at two waves per SIMD) and its out-of-line helpers keep
+// their saved registers there.  The runtime sizes a queue's scratch at the first dispatch that needs it, which held
+// up the first segment scan's walk by ~0.7 ms; this kernel takes that allocation instead, over as many waves as a
+// walk launch can have (256 workgroups of 512), so rsh_ctx_create pays it (on the context stream, the walk's).
+// The rule: this kernel's scratch per lane must be no smaller than chain_advance_kernel's (`make isa F=device_chain`
+// lists both as ScratchSize); raise kWarmScratchWords when a change to the walk takes it past.
+constexpr int kWarmScratchWords = 160;  // 640 B per lane of array (656 with the kernel's own)
 __global__ __launch_bounds__(CHAIN_THREADS) void warm_scratch_kernel(int32_t sel, int32_t* out) {
     volatile int32_t a[kWarmScratchWords];
     for (int i = 0; i < kWarmScratchWords; ++i) a[i] = i ^ sel;

@@ -79,6 +79,17 @@ def test_product_library_has_no_ab_scaffolding():
         assert s not in blob, s
 
 
+def test_md5_asm_inc_is_the_generator_output():
+    """csrc/md5_asm.inc is exactly what tools/gen_md5_asm.py prints: the one MD5 step form the kernels use, no
+    hand edits and no retired forms beside it."""
+    import subprocess
+    import sys
+    pkg = os.path.join(ROOT, "java-rsync_amd")
+    out = subprocess.run([sys.executable, os.path.join(pkg, "tools", "gen_md5_asm.py")], check=True,
+                         capture_output=True, text=True).stdout
+    assert out == open(os.path.join(pkg, "csrc", "md5_asm.inc")).read()
+
+
 def test_library_built_from_these_sources():
     """The build stamps librsynchip.so with its sources' sha256 (lib/librsynchip.srchash); rsync_hip.lib() refuses
     a library whose sources changed since, so no test or bench run measures a stale binary."""

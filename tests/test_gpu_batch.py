@@ -79,7 +79,7 @@ def _pack(ctx, blobs, misalign):
 def test_batch_generator_and_scan_match_oracle(ctx, gather, chain, prefix, rsh_opt):
     # gather=1: each file's full chunks past its last full wave run as a gathered wave of the batched launch
     # (K1Group::count < 64); 0: one per lane in the lane kernel (option k1_gather).  chain=1 (default): the
-    # device walks each file's state machine until a step it leaves to the host resolver (device.hip
+    # device walks each file's state machine until a step it leaves to the host resolver (device_chain.hip
     # chain_advance_kernel); 0: the resolvers from the start (option batch_chain).  prefix: the two-phase walk's
     # prefix in windows (option batch_chain_prefix; -1 = auto, which these small files fit whole: one phase)
     rsh_opt("k1_gather", int(gather))
@@ -395,7 +395,7 @@ def test_batch_waiting_files_keep_their_worker(ctx, rsh_opt):
 
 @pytest.mark.parametrize("helpers", [-1, 0, 3])
 def test_batch_chain_hit_map(ctx, helpers, rsh_opt, capfd):
-    """The phase-0 walk with its hit map (device.hip chain_help / chain_map_tile): while a walk searches tile after
+    """The phase-0 walk with its hit map (device_chain.hip chain_help / chain_map_tile): while a walk searches tile after
     tile, workgroups whose walks have ended (and, helpers = -1 / 3, extra ones) map its prefix ahead of it, and the
     walk takes a tile from the map when every word carries the launch's generation.  Files whose walks search
     hundreds of times before any false hit (random bytes, few keys, every other block replaced), low-entropy ones
@@ -588,6 +588,64 @@ def test_batch_poisoned_walk(ctx, prefix, helpers, rsh_opt):
         assert R.events_as_tuples(evs[i][:sj[i].n_ev], B) == oev, f"form {i}"
         assert (sj[i].literal, sj[i].matched) == (olit, omat)
     assert any(e[0] == R.EV_MATCH for e in expect[1][0]), "form 1: the stale digest must match the carrier"
+
+
+@pytest.mark.parametrize("B", [512, 700])
+def test_batch_chain_inexact_key_set(ctx, B, rsh_opt):
+    """The walk whose LDS key set is not exact (device_chain.hip: *ChainKeySet::full != 0): a table with more distinct
+    weak sums than the set's 2 x 8192 buckets of 2 slots hold, so the tile search confirms every key in the chunk
+    index in global memory (chain_first_hit16's second half, kslots_has in step (2)) and helpers give the file's map
+    up.  B = 512 takes the wide tiles, 700 the narrow ones.  Eight short sources share the one big table, every odd
+    block replaced: some walk to the end, some are poisoned by a false weak hit; with extra helpers and without.
+    Each file against the oracle."""
+    C, dl = 36864, 2
+    n = B * C + 123
+    basis = O.splitmix(n, 0xC0FFEE)
+    oh = O.header(B, dl, n)
+    ow, os_ = O.generator(basis, oh, SEED)
+    assert len(set(np.asarray(ow).tolist())) > 32768  # by counting, the LDS set cannot hold them: the path is taken
+    h = R.header_make(B, dl, n)
+    d_basis = ctx.alloc(n)
+    d_basis.upload(basis)
+    d_w, d_s = ctx.alloc(4 * h.chunk_count), ctx.alloc(dl * h.chunk_count)
+    bj = (R.BlockJob * 1)()
+    bj[0].d_data, bj[0].n, bj[0].h = d_basis.ptr.value, n, h
+    bj[0].d_weak, bj[0].d_strong = d_w.ptr.value, d_s.ptr.value
+    assert R.lib().rsh_block_sums_batch_device(ctx.handle, bj, 1, SEED_NP.ctypes.data) == 0
+    ctx.sync()
+    assert np.array_equal(d_w.download(dtype=np.int32)[:h.chunk_count], ow)
+    assert np.array_equal(d_s.download()[:dl * h.chunk_count], os_)
+
+    srcs, expect = [], []
+    for i in range(8):
+        ns = 48 * B + 37 * i
+        src = basis[:ns].copy()
+        other = O.splitmix(ns, 0xED17 + i)
+        src[:ns // B * B].reshape(-1, B)[1::2] = other[:ns // B * B].reshape(-1, B)[1::2]
+        srcs.append(src.tobytes())
+        oev, _, olit, omat, _ = O.sender(src, oh, ow, os_, SEED)
+        expect.append(([tuple(e) for e in oev], olit, omat))
+    blocks = [omat // B for _, _, omat in expect]
+    assert max(blocks) >= 24 and min(blocks) < 20, blocks  # complete walks and poisoned ones are both compared
+    d_src, soffs = _pack(ctx, srcs, [0] * len(srcs))
+    sj = (R.ScanJob * len(srcs))()
+    evs = []
+    for i, src in enumerate(srcs):
+        cap = len(src) // (10 * B) + 2 * 64 + 64
+        ev = np.zeros(cap, R.EVENT_DTYPE)
+        evs.append(ev)
+        sj[i].d_src, sj[i].n, sj[i].h = d_src.ptr.value + soffs[i], len(src), h
+        sj[i].d_weak, sj[i].d_strong = d_w.ptr.value, d_s.ptr.value
+        sj[i].ev, sj[i].ev_cap = ev.ctypes.data, cap
+    for helpers in (-1, 0):
+        rsh_opt("chain_helpers", helpers)
+        rc = R.lib().rsh_match_scan_batch_device(ctx.handle, sj, len(srcs), SEED_NP.ctypes.data, None)
+        assert rc == 0, (rc, R.lib().rsh_last_error())
+        for i in range(len(srcs)):
+            oev, olit, omat = expect[i]
+            assert sj[i].status == 0
+            assert R.events_as_tuples(evs[i][:sj[i].n_ev], B) == oev, f"file {i}: helpers={helpers}"
+            assert (sj[i].literal, sj[i].matched) == (olit, omat)
 
 
 def test_generation_wrap(rsh_opt):

@@ -1,4 +1,4 @@
-"""Long probe intervals as pass-free segments (device.hip probe_long_kernel) against the oracle.
+"""Long probe intervals as pass-free segments (device_scan.hip probe_long_kernel) against the oracle.
 
 A desynced Sender state (Sender.java:1292-1310, after a FileView flush) is probed by the resolver in batched flush
 chains of up to thousands of intervals of 9B + 1 positions each; their full-window parts run as segments of 16384
