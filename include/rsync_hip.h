@@ -42,6 +42,7 @@ extern "C" {
 #define RSH_E_BUSY (-7)     /* the context is serving a call on another thread               */
 #define RSH_E_NOTFOUND (-8) /* the file does not exist (FileViewNotFound, FileView.java:74-75)    */
 #define RSH_E_OPEN (-9)     /* the file cannot be opened (FileViewOpenFailed, FileView.java:76-78) */
+#define RSH_E_NOSOURCE (-10) /* the context holds no source from its last scan (tiled, trimmed, or reused since) */
 
 /* Checksum.Header; wire order of Connection.sendChecksumHeader (Connection.java:40-45) is
  * chunk_count, block_length, digest_length, remainder (4 x little-endian int32). */
@@ -165,6 +166,42 @@ int rsh_file_md5(const uint8_t* data, int64_t n, uint8_t out[16]);
 int64_t rsh_tokens_size(const rsh_event* ev, int64_t n_ev);
 int rsh_tokens_write(const uint8_t* src, const rsh_event* ev, int64_t n_ev, const uint8_t file_md5[16],
                      uint8_t* out, int64_t cap);
+/* ---- channel bytes from a source in HBM ----
+ * The same bytes framed on the device (token_frame_kernel) when the source the scan read is in HBM: no second pass
+ * over the file, and the literal bytes sent are the ones that were scanned and digested, as in the reference, which
+ * sends them out of the FileView buffer it scanned (Sender.java:794-809).  These forms write bytes [from, from + len)
+ * of the stream rsh_tokens_write would produce into the host buffer `out` (any memory; the library stages through its
+ * own pinned buffers), so that a caller pulls a stream larger than one buffer window by window.  Every event is
+ * checked on the host before anything is launched: RSH_E_INVAL for a literal with offset < 0, length <= 0 or
+ * offset + length > n, for a match with count <= 0, index < 0 or index + count above int32, for an unknown kind, and
+ * for from < 0, len < 0 or from + len > rsh_tokens_size.  len == 0 launches nothing; a stream without literals needs
+ * no source. */
+int rsh_tokens_write_device(rsh_ctx* ctx, const void* d_src, int64_t n, const rsh_event* ev, int64_t n_ev,
+                            const uint8_t file_md5[16], int64_t from, uint8_t* out, int64_t len);
+/* The same over the source the context's last single-file scan left in HBM: rsh_match_scan (block_length > 0),
+ * rsh_match_scan_file below option file_tile_above (a new file included) and rsh_match_scan_pieces when resident
+ * record it; every other call that uses the context's buffers, rsh_ctx_trim and a failed scan drop it (the lifetime of
+ * the events rsh_fetch_events returns).  RSH_E_NOSOURCE when there is none: the caller then replays the literals
+ * from its own copy of the file. */
+int rsh_tokens_write_kept(rsh_ctx* ctx, const rsh_event* ev, int64_t n_ev, const uint8_t file_md5[16], int64_t from,
+                          uint8_t* out, int64_t len);
+/* A segment: every file's whole stream, one job per file, device sources, host outputs; the spans of all files share
+ * the launches.  Per job: RSH_E_NOSPACE with out_len = the size needed when out_cap is short, RSH_E_INVAL for that
+ * file's bad events; the other files are still written.  Returns RSH_OK or the first failing job's status. */
+typedef struct {
+    const void* d_src;
+    int64_t n;
+    const rsh_event* ev;   /* host */
+    int64_t n_ev;
+    uint8_t file_md5[16];
+    uint8_t* out;          /* host, caller-owned: out_cap bytes */
+    int64_t out_cap;
+    int64_t out_len;       /* out: the stream's size */
+    int32_t status;        /* out */
+    int32_t reserved;
+} rsh_token_job;
+int rsh_tokens_write_batch_device(rsh_ctx* ctx, rsh_token_job* jobs, int32_t njobs);
+
 /* Generator channel bytes: header + per chunk putInt(weak) + digest_length bytes. */
 int64_t rsh_generator_bytes(const rsh_header* h, const int32_t* weak, const uint8_t* strong, uint8_t* out,
                             int64_t cap);

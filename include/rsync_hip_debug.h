@@ -7,7 +7,7 @@
  * Tests force rare paths with them; a few are tunables: k1_gather, k1_shift,
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
- * fault_inject.
+ * fault_inject, tokens_span, tokens_piece.
  */
 #ifndef RSYNC_HIP_DEBUG_H
 #define RSYNC_HIP_DEBUG_H
@@ -54,6 +54,14 @@ int rsh_debug_k1_clock(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t bloc
  * every job's status after the merge.  Returns the driver's status. */
 int rsh_debug_multi_selftest(const int64_t* bytes, int32_t njobs, int32_t nparts, int32_t fail_part, int32_t* part_out,
                              int32_t* order_out, int32_t* status_out);
+
+/* The span planner of rsh_tokens_write_device without a device: checks the events against a source of n bytes as the
+ * entry points do (their RSH_E_INVAL cases), plans the spans of stream bytes [from, from + len) at `span` bytes per
+ * descriptor (0: option tokens_span) and executes them over the host source `src` with a host stand-in that runs
+ * token_frame_kernel's per-span arithmetic (token_frame.h), writing to `out`.  *n_desc: the descriptor count. */
+int rsh_debug_tokens_selftest(const uint8_t* src, int64_t n, const rsh_event* ev, int64_t n_ev,
+                              const uint8_t file_md5[16], int64_t from, uint8_t* out, int64_t len, int64_t span,
+                              int64_t* n_desc);
 
 #ifdef __cplusplus
 }

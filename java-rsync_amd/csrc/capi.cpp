@@ -119,6 +119,7 @@ const char* rsh_strerror(int status) {
         case RSH_E_BUSY: return "context in use by another thread";
         case RSH_E_NOTFOUND: return "file not found (FileViewNotFound)";
         case RSH_E_OPEN: return "file cannot be opened (FileViewOpenFailed)";
+        case RSH_E_NOSOURCE: return "the context holds no source from its last scan";
         default: return "unknown status";
     }
 }
@@ -205,7 +206,8 @@ int rsh_ctx_trim(rsh_ctx* ctx) {
     for (DevBuf* b : {&ctx->data, &ctx->weak, &ctx->strong, &ctx->seg_data, &ctx->seg_tab, &ctx->rcv[0], &ctx->rcv[1],
                       &ctx->rcv_ops[0], &ctx->rcv_ops[1], &ctx->out})
         b->release();
-    for (PinnedBuf* b : {&ctx->h_stage, &ctx->h_rcv_ops[0], &ctx->h_rcv_ops[1], &ctx->h_out})
+    for (PinnedBuf* b : {&ctx->h_stage, &ctx->h_rcv_ops[0], &ctx->h_rcv_ops[1], &ctx->h_out, &ctx->h_tok, &ctx->h_tokd[0],
+                         &ctx->h_tokd[1]})
         b->release();
     if (ctx->h_win.cap > (1u << 20)) ctx->h_win.release();  // (a Receiver pass's pieces; the scan's windows are small)
     // The batched scan's state stays: its chunk index, hit map, descriptors, pinned event and
@@ -364,6 +366,9 @@ int rsh_match_scan(rsh_ctx* ctx, const uint8_t* src, int64_t n, const rsh_header
     if (literal) *literal = r.literal;
     if (matched) *matched = r.matched;
     if (stats) *stats = r.stats;
+    // the uploaded source stays in HBM for rsh_tokens_write_kept (a new file, block_length 0, is never uploaded)
+    if (n == 0) ctx->keep_source(nullptr, 0);
+    else if (h->block_length > 0) ctx->keep_source(ctx->data.p, n);
     return emit_events(ctx, r, ev, ev_cap, n_ev);
 }
 
@@ -417,7 +422,7 @@ int rsh_match_scan_tiled(rsh_ctx* ctx, const uint8_t* src, int64_t n, const rsh_
 
 int rsh_fetch_events(rsh_ctx* ctx, rsh_event* ev, int64_t ev_cap, int64_t* n_ev) {
     if (!ctx || !n_ev) return RSH_E_INVAL;
-    RSH_CLAIM(ctx);
+    RSH_CLAIM_KEEP(ctx);
     *n_ev = (int64_t)ctx->last_ev.size();
     if (*n_ev > ev_cap || (!ev && *n_ev > 0)) return RSH_E_NOSPACE;
     if (*n_ev > 0) memcpy(ev, ctx->last_ev.data(), ctx->last_ev.size() * sizeof(rsh_event));

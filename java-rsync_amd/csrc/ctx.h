@@ -235,6 +235,19 @@ struct rsh_ctx {
         return stamp_seq;
     }
     std::vector<rsh_event> last_ev;  // kept when the caller's event buffer was too small
+    // The source the last single-file scan left in HBM (rsh_tokens_write_kept): its first byte and its length, -1 when
+    // there is none.  Recorded by the scans that assemble the whole source in `data`; dropped by every other call that
+    // claims the context (CtxClaim: any of them may reuse or release `data`), so it lives as long as last_ev does.
+    const uint8_t* kept_src = nullptr;
+    int64_t kept_n = -1;
+    void keep_source(const void* d, int64_t n) {
+        kept_src = static_cast<const uint8_t*>(d);
+        kept_n = n;
+    }
+    // rsh_tokens_write_*: two pinned staging pieces the kernel fills in turn while the host copies the other out, each
+    // with its span descriptors and the event that marks its launch done (tokens.cpp)
+    PinnedBuf h_tok, h_tokd[2];
+    hipEvent_t ev_tok[2] = {nullptr, nullptr};
     std::atomic<bool> busy{false};   // the staging buffers and last_ev serve one call at a time
     rsh::BatchState* batch = nullptr;  // buffers of the batched (multi-file) entry points, on first use
     ~rsh_ctx() {
@@ -246,7 +259,8 @@ struct rsh_ctx {
             b->release();
         for (PinnedBuf* b : {&h_weak, &h_strong, &h_aw, &h_as, &h_fl, &h_pw[0], &h_ps[0], &h_pw[1], &h_ps[1], &h_lead, &h_pos, &h_out, &h_iv,
                              &h_tiles, &h_keys, &h_first, &h_win, &h_ptiles, &h_psegs, &h_hit, &h_win0, &h_pend, &h_bucket, &h_files,
-                             &h_stage, &h_rcv_ops[0], &h_rcv_ops[1], &h_prep, &h_stamps, &h_fgw, &h_fjobs, &h_fout})
+                             &h_stage, &h_rcv_ops[0], &h_rcv_ops[1], &h_prep, &h_stamps, &h_fgw, &h_fjobs, &h_fout,
+                             &h_tok, &h_tokd[0], &h_tokd[1]})
             b->release();
         if (abort_word) (void)hipFree(abort_word);
         if (ev_in) (void)hipEventDestroy(ev_in);
@@ -256,7 +270,7 @@ struct rsh_ctx {
             if (e) (void)hipEventDestroy(e);
         if (ev_flags) (void)hipEventDestroy(ev_flags);
         if (ev_prep) (void)hipEventDestroy(ev_prep);
-        for (hipEvent_t e : {ev_k1a, ev_k1b, ev_gen_a, ev_gen_b, ev_rs_tail})
+        for (hipEvent_t e : {ev_k1a, ev_k1b, ev_gen_a, ev_gen_b, ev_rs_tail, ev_tok[0], ev_tok[1]})
             if (e) (void)hipEventDestroy(e);
         if (aux) (void)hipStreamDestroy(aux);
         if (phase) (void)hipStreamDestroy(phase);
@@ -282,22 +296,28 @@ inline void note_error(hipError_t e, int line, const char* file = "capi.cpp") {
 namespace rshi {
 
 // Claims a context for one call that uses its buffers; a second thread gets RSH_E_BUSY instead of
-// racing on them (one rsh_ctx per calling thread, rsync_hip.h).
+// racing on them (one rsh_ctx per calling thread, rsync_hip.h).  A claim drops the kept source (rsh_ctx::kept_src)
+// unless the call only reads what the last scan left (keep: rsh_fetch_events, rsh_tokens_write_*).
 struct CtxClaim {
     rsh_ctx* c;
     bool held;
-    explicit CtxClaim(rsh_ctx* ctx) : c(ctx), held(!ctx->busy.exchange(true, std::memory_order_acquire)) {}
+    explicit CtxClaim(rsh_ctx* ctx, bool keep = false)
+        : c(ctx), held(!ctx->busy.exchange(true, std::memory_order_acquire)) {
+        if (held && !keep) ctx->keep_source(nullptr, -1);
+    }
     ~CtxClaim() {
         if (held) c->busy.store(false, std::memory_order_release);
     }
 };
 
-#define RSH_CLAIM(ctx)                                                                   \
-    CtxClaim claim_(ctx);                                                                \
+#define RSH_CLAIM_AS(ctx, keep)                                                          \
+    CtxClaim claim_(ctx, keep);                                                          \
     if (!claim_.held) {                                                                  \
         snprintf(g_last_err, sizeof(g_last_err), "context in use by another thread");   \
         return RSH_E_BUSY;                                                               \
     }
+#define RSH_CLAIM(ctx) RSH_CLAIM_AS(ctx, false)
+#define RSH_CLAIM_KEEP(ctx) RSH_CLAIM_AS(ctx, true)
 
 // Header consistency for the Generator side (3-arg ctor semantics, Checksum.java:94-113).
 inline int check_generator_header(int64_t n, const rsh_header* h) {

@@ -331,6 +331,12 @@ hipError_t launch_gather_ops(const GatherOp* ops, uint32_t n, hipStream_t s, int
 #ifdef RSH_KBENCH
 hipError_t launch_gather_ops_variant(int v, const GatherOp* ops, uint32_t n, hipStream_t s);  // A/Bs (kbench)
 #endif
+// The Sender's channel bytes from a source in HBM (device_tokens.hip, token_frame.h): spans in
+// device or pinned host memory; max_len: the longest span's bytes (a span is cut over several workgroups);
+// dst_on_host: the spans' destinations are pinned host memory (plain stores).
+struct TokSpan;
+hipError_t launch_token_frame(const TokSpan* spans, uint32_t n, uint32_t max_len, bool dst_on_host, hipStream_t s);
+hipError_t launch_warm_tokens(hipStream_t s);
 // Probe hashes of many files (slots cleared by the caller): keys[i] into slots/mask.
 struct TableEnt {
     unsigned long long* slots;

@@ -361,6 +361,9 @@ int rsh_match_scan_file(rsh_ctx* ctx, const char* path, int64_t size, const rsh_
     if (literal) *literal = r.literal;
     if (matched) *matched = r.matched;
     if (stats) *stats = r.stats;
+    // The bytes that were scanned and digested stay in HBM for rsh_tokens_write_kept (a new file's too: its copies
+    // are complete, the digest thread waited for each) -- zero fill after a read error included.
+    ctx->keep_source(size > 0 ? ctx->data.p : nullptr, size);
     return emit_events(ctx, r, ev, ev_cap, n_ev);
 }
 

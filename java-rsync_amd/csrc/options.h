@@ -38,6 +38,8 @@ enum Opt : int {
     OPT_BATCH_WARM,        // rsh_ctx_create pre-sizes the batched scan's state for this many 128 MiB files (0: none)
     OPT_FAULT_INJECT,      // tests only: bit 0 a segment / Receiver pass's HBM allocation fails, bit 1 a segment's copies fail,
                            // bit 2 bits 0 / 1 only on member 1 of a multi-context call (multi.cpp)
+    OPT_TOKENS_SPAN,       // rsh_tokens_write_*device / _kept: stream bytes per span descriptor
+    OPT_TOKENS_PIECE,      // ... bytes per pinned staging buffer (two of them: one filled while the other is copied out)
     OPT_COUNT
 };
 
@@ -53,7 +55,7 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"file_tile", 4LL << 30},   {"file_tile_above", 32LL << 30}, {"probe_long", 1},
     {"segment_bytes", 16LL << 30}, {"md5_width", 0},    {"chain_helpers", -1},
     {"chain_map_bytes", 1LL << 30}, {"time_gen", 1},    {"batch_warm", 128},
-    {"fault_inject", 0},
+    {"fault_inject", 0},        {"tokens_span", 256LL << 10}, {"tokens_piece", 8LL << 20},
 };
 
 inline const OptInfo* opt_info() { return kOpts; }

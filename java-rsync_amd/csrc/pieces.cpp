@@ -165,6 +165,9 @@ int rsh_match_scan_pieces(rsh_ctx* ctx, const rsh_piece* pieces, int32_t npieces
     if (literal) *literal = r.literal;
     if (matched) *matched = r.matched;
     if (stats) *stats = r.stats;
+    // the source stays in HBM for rsh_tokens_write_kept (a tiled scan leaves only its last tile)
+    if (n == 0) ctx->keep_source(nullptr, 0);
+    else if (h->block_length > 0 && n <= resident_max()) ctx->keep_source(ctx->data.p, n);
     return emit_events(ctx, r, ev, ev_cap, n_ev);
 }
 

@@ -208,6 +208,32 @@ final class NativeChecksum implements AutoCloseable {
         }
     }
 
+    /**
+     * Sender.java:794-809,1274,1316,1148 for a whole file: bytes [from, from + len) of the channel bytes of the events
+     * a matchScan* call just returned -- the 8 KiB tokens, putInt(-(index + 1)) per matched chunk, putInt(0) and
+     * fileMd5 -- framed by the library from the source that scan left in HBM, into the direct buffer out.  False
+     * when the context no longer holds that source (a tiled scan, trim(), any other call since): the caller then
+     * replays the events itself.
+     */
+    boolean tokensKept(long[] events, int nEv, byte[] fileMd5, long from, ByteBuffer out, long len) {
+        lock.lock();
+        try {
+            return tokensKept(handle(), events, nEv, fileMd5, from, out, len);
+        } finally {
+            lock.unlock();
+        }
+    }
+
+    /** The size of those channel bytes (rsh_tokens_size over the quadruples). */
+    static long tokensSize(long[] events, int nEv) {
+        long size = 4 + 16;
+        for (int i = 0; i < nEv; i++) {
+            long len = events[4 * i + 2];
+            size += events[4 * i] == 1 ? len + 4 * ((len + 8191) / 8192) : 4 * (events[4 * i + 3] >> 32);
+        }
+        return size;
+    }
+
     /** As blockSums, reading the file natively (FileView semantics); true = read error (FileViewException). */
     boolean blockSumsFile(String path, long size, Checksum.Header h, byte[] seed, int[] weak, byte[] strong) {
         lock.lock();
@@ -349,6 +375,9 @@ final class NativeChecksum implements AutoCloseable {
     static native void ctxDestroy(long ctx);
 
     static native void ctxTrim(long ctx);
+
+    static native boolean tokensKept(long ctx, long[] events, int nEv, byte[] fileMd5, long from, ByteBuffer out,
+            long len);
 
     static native int blockLengthFor(long fileSize);
 

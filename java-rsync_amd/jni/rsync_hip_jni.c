@@ -28,7 +28,8 @@
  *   blockSumsBatchMulti / matchScanBatchMulti  the same over the calling thread's contexts on the node's GPUs
  *                                      (rsh_*_batch_multi: the segment's files split over them).
  * The Sender replays the returned events through its own sendDataFrom/putInt so channel framing is
- * untouched (Sender.java:794-809); INTEGRATION.md shows the replay for each form.
+ * untouched (Sender.java:794-809); INTEGRATION.md shows the replay for each form.  tokensKept is that replay done
+ * by the library from the source the scan left in HBM (the path form's first choice).
  *
  * Build (needs a JDK): make -C java-rsync_amd jni JAVA_HOME=/path/to/jdk
  */
@@ -836,6 +837,54 @@ JNIEXPORT jlongArray JNICALL Java_com_github_java_rsync_internal_session_NativeC
     jlongArray out = scan_segment(env, cs, n, src, filePieces, sizes, hdrs, weak, strong, seed, fileMd5Out, perFileOut);
     free(cs);
     return out;
+}
+
+/* ---- Sender.sendDataFrom / putInt replay from the source the last scan left in HBM (rsh_tokens_write_kept) ----
+ * events: the quadruples a matchScan* call returned ({kind, offset, length, index | (count << 32)}), nEv of them;
+ * out: a direct ByteBuffer that receives bytes [from, from + len) of the file's channel bytes (the tokens, putInt(0),
+ * md5).  Returns false when the context holds no source (RSH_E_NOSOURCE: a tiled scan, a trim, another call since):
+ * the caller then replays the literals with its positional reads. */
+JNIEXPORT jboolean JNICALL Java_com_github_java_rsync_internal_session_NativeChecksum_tokensKept(
+    JNIEnv* env, jclass cls, jlong ctx, jlongArray events, jint nEv, jbyteArray md5, jlong from, jobject out, jlong len) {
+    (void)cls;
+    rsh_ctx* c = ctx_of(env, ctx);
+    if (!c) return JNI_FALSE;
+    if (nEv < 0 || !md5 || (*env)->GetArrayLength(env, md5) != 16 ||
+        (nEv > 0 && (!events || (jlong)(*env)->GetArrayLength(env, events) < 4 * (jlong)nEv))) {
+        throw_class(env, "java/lang/IllegalArgumentException",
+                    nEv > 0 && md5 ? "the events array holds fewer than nEv entries" : "bad event count or md5");
+        return JNI_FALSE;
+    }
+    uint8_t* o = (uint8_t*)direct_bytes(env, out, len);
+    if (!o) return JNI_FALSE;
+    jbyte m[16];
+    (*env)->GetByteArrayRegion(env, md5, 0, 16, m);
+    enum { CHUNK = 4096 };
+    rsh_event* ev = (rsh_event*)malloc(((size_t)nEv + 1) * sizeof(rsh_event));
+    jlong* q = (jlong*)malloc(sizeof(jlong) * 4 * CHUNK);
+    int rc = (ev && q) ? RSH_OK : RSH_E_NOMEM;
+    for (jint i = 0; rc == RSH_OK && i < nEv; i += CHUNK) {
+        const jint k = nEv - i < CHUNK ? nEv - i : CHUNK;
+        (*env)->GetLongArrayRegion(env, events, 4 * i, 4 * k, q);
+        for (jint j = 0; j < k; ++j) {
+            rsh_event* e = &ev[i + j];
+            e->kind = (int32_t)q[4 * j];
+            e->offset = q[4 * j + 1];
+            e->length = q[4 * j + 2];
+            e->index = (int32_t)(uint32_t)q[4 * j + 3];
+            e->count = (int32_t)(q[4 * j + 3] >> 32);
+            e->reserved = 0;
+        }
+    }
+    if (rc == RSH_OK) rc = rsh_tokens_write_kept(c, ev, nEv, (const uint8_t*)m, from, o, len);
+    free(q);
+    free(ev);
+    if (rc == RSH_E_NOSOURCE) return JNI_FALSE;
+    if (rc != RSH_OK) {
+        throw_status(env, rc);
+        return JNI_FALSE;
+    }
+    return JNI_TRUE;
 }
 
 /* ---- Receiver.combineDataToFile (Receiver.java:459-555) over direct buffers ----

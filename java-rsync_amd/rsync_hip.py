@@ -24,7 +24,7 @@ LIB_PATH = os.environ.get("RSH_LIB") or os.path.join(HERE, "lib", "librsynchip.s
 
 RSH_OK, RSH_E_INVAL, RSH_E_PROTOCOL, RSH_E_OVERFLOW, RSH_E_NOSPACE, RSH_E_DEVICE, RSH_E_NOMEM, RSH_E_BUSY = \
     0, -1, -2, -3, -4, -5, -6, -7
-RSH_E_NOTFOUND, RSH_E_OPEN = -8, -9
+RSH_E_NOTFOUND, RSH_E_OPEN, RSH_E_NOSOURCE = -8, -9, -10
 EV_LITERAL, EV_MATCH = 1, 2
 
 
@@ -46,6 +46,11 @@ class ContextBusyError(RuntimeError):
 
 class DeviceError(RuntimeError):
     """HIP failure or no gfx950 device."""
+
+
+class NoSourceError(RuntimeError):
+    """RSH_E_NOSOURCE: the context holds no source from its last scan (tiled, trimmed, or its buffers reused since);
+    the caller replays the literals from its own copy of the file."""
 
 
 class Header(ctypes.Structure):
@@ -126,6 +131,13 @@ class ScanBatchJob(ctypes.Structure):
                 ("matched", ctypes.c_int64), ("file_md5", ctypes.c_uint8 * 16)]
 
 
+class TokenJob(ctypes.Structure):
+    """rsh_token_job: one file of rsh_tokens_write_batch_device (device source, host events and output)."""
+    _fields_ = [("d_src", ctypes.c_void_p), ("n", ctypes.c_int64), ("ev", ctypes.c_void_p), ("n_ev", ctypes.c_int64),
+                ("file_md5", ctypes.c_uint8 * 16), ("out", ctypes.c_void_p), ("out_cap", ctypes.c_int64),
+                ("out_len", ctypes.c_int64), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class Md5Job(ctypes.Structure):
     """rsh_md5_job: one file of rsh_file_md5_batch."""
     _fields_ = [("pieces", ctypes.POINTER(Piece)), ("npieces", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -141,10 +153,12 @@ EXPORTS = ["rsh_abi_version", "rsh_strerror", "rsh_last_error", "rsh_device_coun
            "rsh_header_validate", "rsh_block_sums", "rsh_block_sums_device", "rsh_ctx_sync", "rsh_ctx_trim", "rsh_match_scan",
            "rsh_match_scan_device", "rsh_match_scan_tiled", "rsh_fetch_events", "rsh_file_md5", "rsh_tokens_size", "rsh_tokens_write", "rsh_generator_bytes",
            "rsh_block_sums_batch_device", "rsh_match_scan_batch_device", "rsh_receiver_combine",
-           "rsh_receiver_combine_device", "rsh_receiver_combine_batch", "rsh_block_sums_file", "rsh_match_scan_file", "rsh_block_sums_pieces", "rsh_match_scan_pieces", "rsh_block_sums_batch", "rsh_match_scan_batch", "rsh_block_sums_batch_multi", "rsh_match_scan_batch_multi", "rsh_receiver_combine_batch_multi", "rsh_shard_files", "rsh_file_md5_batch", "rsh_dev_alloc", "rsh_dev_free", "rsh_memcpy_h2d", "rsh_memcpy_d2h", "rsh_fill_splitmix_device"]
+           "rsh_receiver_combine_device", "rsh_receiver_combine_batch", "rsh_block_sums_file", "rsh_match_scan_file", "rsh_block_sums_pieces", "rsh_match_scan_pieces", "rsh_block_sums_batch", "rsh_match_scan_batch", "rsh_block_sums_batch_multi", "rsh_match_scan_batch_multi", "rsh_receiver_combine_batch_multi", "rsh_shard_files", "rsh_file_md5_batch", "rsh_dev_alloc", "rsh_dev_free", "rsh_memcpy_h2d", "rsh_memcpy_d2h", "rsh_fill_splitmix_device",
+           "rsh_tokens_write_device", "rsh_tokens_write_kept", "rsh_tokens_write_batch_device"]
 # include/rsync_hip_debug.h (testing / diagnostics ABI)
 DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_reset_options", "rsh_debug_k1_clock",
-                 "rsh_debug_streams_busy", "rsh_debug_kernel_ms", "rsh_debug_multi_selftest", "rsh_debug_generation"]
+                 "rsh_debug_streams_busy", "rsh_debug_kernel_ms", "rsh_debug_multi_selftest", "rsh_debug_generation",
+                 "rsh_debug_tokens_selftest"]
 
 _LIB = None
 
@@ -246,6 +260,10 @@ def lib():
         "rsh_debug_generation": ([P, I32, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
         "rsh_debug_kernel_ms": ([P, I32, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "rsh_debug_multi_selftest": ([P, I32, I32, I32, P, P, P], ctypes.c_int),
+        "rsh_tokens_write_device": ([P, P, I64, P, I64, P, I64, P, I64], ctypes.c_int),
+        "rsh_tokens_write_kept": ([P, P, I64, P, I64, P, I64], ctypes.c_int),
+        "rsh_tokens_write_batch_device": ([P, ctypes.POINTER(TokenJob), I32], ctypes.c_int),
+        "rsh_debug_tokens_selftest": ([P, I64, P, I64, P, I64, P, I64, I64, ctypes.POINTER(I64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -273,6 +291,8 @@ def _check(rc):
         raise FileViewNotFound(msg)
     if rc == RSH_E_OPEN:
         raise FileViewOpenFailed(msg)
+    if rc == RSH_E_NOSOURCE:
+        raise NoSourceError(msg)
     detail = lib().rsh_last_error().decode()
     raise DeviceError(f"{msg}: {detail}" if detail else msg)
 
@@ -365,6 +385,29 @@ def tokens(src, ev, file_md5_bytes):
     fm = np.frombuffer(file_md5_bytes, np.uint8).copy()
     _check(lib().rsh_tokens_write(_ptr(a), _ptr(ev) if n else None, n, _ptr(fm), _ptr(out), size))
     return out.tobytes()
+
+
+def tokens_size(ev):
+    """rsh_tokens_size: the bytes of the stream tokens() writes for these events."""
+    ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+    return lib().rsh_tokens_size(_ptr(ev) if ev.size else None, ev.size)
+
+
+def tokens_selftest(src, ev, file_md5_bytes, start=0, length=None, span=0, out=None):
+    """rsh_debug_tokens_selftest: the device forms' validator, span planner and a host stand-in of the kernel over the
+    host source `src`: (bytes [start, start + length) of the stream, descriptor count).  out: a uint8 array to write
+    into (any alignment) instead of a fresh one."""
+    a = _u8(src)
+    ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+    fm = np.frombuffer(file_md5_bytes, np.uint8).copy()
+    if length is None:
+        length = tokens_size(ev) - start
+    if out is None:
+        out = np.zeros(max(length, 1), np.uint8)
+    nd = ctypes.c_int64()
+    _check(lib().rsh_debug_tokens_selftest(_ptr(a) if a.size else None, a.size, _ptr(ev) if ev.size else None, ev.size,
+                                           _ptr(fm), start, _ptr(out), length, span, ctypes.byref(nd)))
+    return out[:max(length, 0)].tobytes(), nd.value
 
 
 def set_option(name, value):
@@ -640,6 +683,71 @@ class Context:
             rc = lib().rsh_fetch_events(self._p, _ptr(ev), n_ev.value, ctypes.byref(n_ev))
         _check(rc)
         return ev[:n_ev.value], fm.tobytes(), lit.value, mat.value, stats.as_dict(), bool(err.value)
+
+    @staticmethod
+    def _guarded(length):
+        """A host output buffer with 64 guard bytes of 0xA5 on each side: (whole array, the view to write into)."""
+        whole = np.full(length + 128, 0xA5, np.uint8)
+        return whole, whole[64:64 + length]
+
+    @staticmethod
+    def _guards_intact(whole):
+        return bool((whole[:64] == 0xA5).all() and (whole[-64:] == 0xA5).all())
+
+    def _tokens_window(self, call, ev, md5, start, length):
+        ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+        fm = np.frombuffer(bytes(md5), np.uint8).copy()
+        if length is None:
+            length = tokens_size(ev) - start
+        whole, out = self._guarded(max(length, 0))
+        rc = call(_ptr(ev) if ev.size else None, ev.size, _ptr(fm), start, _ptr(out) if out.size else None, length)
+        if not self._guards_intact(whole):
+            raise AssertionError("token bytes were written outside the output buffer")
+        _check(rc)
+        return out.tobytes()
+
+    def tokens_device(self, dbuf_or_ptr, n, ev, md5, start=0, length=None):
+        """rsh_tokens_write_device: bytes [start, start + length) (length None: to the end) of the Sender's channel
+        bytes for the events, framed on the device from the source in HBM (a DeviceBuffer or a device address, n
+        bytes).  Equals tokens(src, ev, md5)[start:start + length].  The output buffer has guard bytes on both sides,
+        which are checked after the call."""
+        ptr = dbuf_or_ptr.ptr if isinstance(dbuf_or_ptr, DeviceBuffer) else ctypes.c_void_p(dbuf_or_ptr or None)
+        return self._tokens_window(
+            lambda e, ne, fm, a, o, ln: lib().rsh_tokens_write_device(self._p, ptr, n, e, ne, fm, a, o, ln),
+            ev, md5, start, length)
+
+    def tokens_kept(self, ev, md5, start=0, length=None):
+        """rsh_tokens_write_kept: as tokens_device over the source this context's last single-file scan left in HBM;
+        NoSourceError when there is none."""
+        return self._tokens_window(
+            lambda e, ne, fm, a, o, ln: lib().rsh_tokens_write_kept(self._p, e, ne, fm, a, o, ln), ev, md5, start,
+            length)
+
+    def tokens_batch_device(self, jobs):
+        """rsh_tokens_write_batch_device: a segment's streams in one call.  jobs = [(dbuf_or_ptr, n, ev, md5[, out_cap])]
+        (out_cap: the output capacity to offer instead of the stream's size) -> (the call's status,
+        [(status, stream bytes or None, out_len)])."""
+        tj = (TokenJob * max(len(jobs), 1))()
+        keep = []
+        for i, job in enumerate(jobs):
+            d, n, ev, md5 = job[:4]
+            ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+            cap = job[4] if len(job) > 4 else tokens_size(ev)
+            whole, out = self._guarded(max(cap, 0))
+            keep.append((ev, whole, out))
+            ptr = d.ptr.value if isinstance(d, DeviceBuffer) else d
+            tj[i].d_src, tj[i].n = ptr or None, n
+            tj[i].ev, tj[i].n_ev = (ev.ctypes.data if ev.size else None), ev.size
+            tj[i].file_md5[:] = list(bytes(md5))
+            tj[i].out, tj[i].out_cap = out.ctypes.data, cap
+        rc = lib().rsh_tokens_write_batch_device(self._p, tj, len(jobs))
+        res = []
+        for i, (ev, whole, out) in enumerate(keep):
+            if not self._guards_intact(whole):
+                raise AssertionError(f"job {i}: token bytes were written outside the output buffer")
+            ok = tj[i].status == RSH_OK
+            res.append((tj[i].status, out[:tj[i].out_len].tobytes() if ok else None, tj[i].out_len))
+        return rc, res
 
     def receiver_combine_batch(self, files, statuses=None):
         """A segment's Receiver from host memory (rsh_receiver_combine_batch; Receiver.receiveFiles):

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "device.h"
+#include "token_frame.h"
 
 #define CK(x)                                                                   \
     do {                                                                        \
@@ -82,8 +83,82 @@ static int gather_main(int argc, char** argv) {
     return 0;
 }
 
+// KBENCH_TOKENS=<span bytes>: token_frame_kernel (device_tokens.hip) framing the first <MiB> of one all-literal event's
+// stream from HBM into HBM, in spans of that many bytes (0: the library's default, 256 KiB), against the production
+// gather (gather_ops_kernel_t<1024, 4, true, true>, KBENCH_GATHER's variant 6 with 1 MiB ops) copying the same number
+// of bytes: the same traffic without the framing.  The two alternate rep by rep in one process.
+static int tokens_main(int argc, char** argv) {
+    const int64_t n = (int64_t)atoll(argv[1]) << 20;
+    int64_t span = atoll(getenv("KBENCH_TOKENS"));
+    if (span <= 0) span = 256 << 10;
+    const int reps = atoi(argv[4]);
+    hipStream_t s;
+    CK(hipStreamCreate(&s));
+    uint8_t *src, *dst;
+    CK(hipMalloc(&src, n));
+    CK(hipMalloc(&dst, n));
+    CK(rsh::launch_fill_splitmix(src, n, 0x5EED, 0, s));
+    const rsh_event e{0, n, RSH_EV_LITERAL, 0, 0, 0};  // its stream is n + 4 ceil(n / 8192) bytes: the window is [0, n)
+    std::vector<rsh::TokSpan> spans;
+    rsh::tok_plan_event(e, src, 0, n, dst, span, spans);
+    rsh::TokSpan* d_spans;
+    CK(hipMalloc(&d_spans, spans.size() * sizeof(rsh::TokSpan)));
+    CK(hipMemcpy(d_spans, spans.data(), spans.size() * sizeof(rsh::TokSpan), hipMemcpyHostToDevice));
+    const int64_t op = 1 << 20;
+    std::vector<rsh::GatherOp> ops;
+    for (int64_t o = 0; o < n; o += op) ops.push_back(rsh::GatherOp{src + o, dst + o, std::min(op, n - o)});
+    rsh::GatherOp* d_ops;
+    CK(hipMalloc(&d_ops, ops.size() * sizeof(rsh::GatherOp)));
+    CK(hipMemcpy(d_ops, ops.data(), ops.size() * sizeof(rsh::GatherOp), hipMemcpyHostToDevice));
+    // parity: three 20 KiB ranges of the framed window against the layout computed on the host
+    CK(hipMemset(dst, 0, n));
+    CK(rsh::launch_token_frame(d_spans, (uint32_t)spans.size(), (uint32_t)std::min(span, n), false, s));
+    CK(hipStreamSynchronize(s));
+    bool same = true;
+    const int64_t chk = 20 << 10;
+    std::vector<uint8_t> got((size_t)chk), hs((size_t)chk + 8200);  // (the range's tokens' source bytes)
+    for (int64_t q : {(int64_t)0, n / 3, n - chk}) {
+        const int64_t k0 = q / rsh::kTokStride;  // source bytes of tokens k0 .. from k0 * 8192 on
+        CK(hipMemcpy(got.data(), dst + q, (size_t)chk, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(hs.data(), src + k0 * rsh::kTokData, (size_t)std::min<int64_t>((int64_t)hs.size(), n - k0 * rsh::kTokData), hipMemcpyDeviceToHost));
+        for (int64_t t = q; t < q + chk; ++t) {
+            const int64_t k = t / rsh::kTokStride, r = t % rsh::kTokStride;
+            const uint8_t want = r < 4 ? (uint8_t)(rsh::tok_len(n, (uint32_t)k) >> (8 * r))
+                                       : hs[(size_t)((k - k0) * rsh::kTokData + r - 4)];
+            same = same && got[(size_t)(t - q)] == want;
+        }
+    }
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    float best[2] = {1e30f, 1e30f}, tot[2] = {0, 0};
+    for (int r = 0; r < reps + 1; ++r) {  // (the first round warms both up)
+        for (int w = 0; w < 2; ++w) {
+            CK(hipEventRecord(e0, s));
+            if (w == 0) CK(rsh::launch_token_frame(d_spans, (uint32_t)spans.size(), (uint32_t)std::min(span, n), false, s));
+            else CK(rsh::launch_gather_ops_variant(6, d_ops, (uint32_t)ops.size(), s));
+            CK(hipEventRecord(e1, s));
+            CK(hipEventSynchronize(e1));
+            float ms;
+            CK(hipEventElapsedTime(&ms, e0, e1));
+            if (r == 0) continue;
+            best[w] = ms < best[w] ? ms : best[w];
+            tot[w] += ms;
+        }
+    }
+    const char* name[2] = {"token_frame", "gather <1024,4,nt,nt>"};
+    for (int w = 0; w < 2; ++w)
+        printf("%-22s n=%lld %s=%lld descriptors=%zu  avg %.3f ms  best %.3f ms  %.1f GB/s (read+write; %.3f of 8 TB/s)%s\n",
+               name[w], (long long)n, w ? "op" : "span", (long long)(w ? op : span), w ? ops.size() : spans.size(),
+               tot[w] / reps, best[w], 2.0 * n / (tot[w] / reps / 1e3) / 1e9, 2.0 * n / (tot[w] / reps / 1e3) / 8e12,
+               w ? "" : (same ? "  frame=ok" : "  frame=MISMATCH"));
+    printf("token_frame / gather: avg %.3f  best %.3f\n", tot[0] / tot[1], best[0] / best[1]);
+    return same ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 6 && getenv("KBENCH_GATHER")) return gather_main(argc, argv);
+    if (argc >= 5 && getenv("KBENCH_TOKENS")) return tokens_main(argc, argv);
     if (argc < 6) {
         fprintf(stderr, "usage: kbench <MiB> <B> <dl> <reps> <variant>...\n");
         return 2;
