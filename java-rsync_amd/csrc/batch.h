@@ -1,8 +1,8 @@
 // batch.h -- the batched Sender scan's shared state (not part of the C-ABI): the per-context BatchState, a file's
 // resolver (FileScan: its table, state and BatchBackend), the requests its fiber posts (Req) and the rounds that answer
-// them (Batch).  batch.cpp plans a segment's scan and drives its chain walks (scan_batch); batch_pool.cpp runs the
-// resolvers that are left as fibers on a pool of worker threads and answers their device questions one round at a
-// time (run_resolvers, serve_round).
+// them (Batch).  batch.cpp lays a segment's scan out (SegmentLayout) and drives its chain walks (scan_batch: the steps
+// of its Scan); batch_pool.cpp runs the resolvers that are left as fibers on a pool of worker threads and answers their
+// device questions one round at a time (run_resolvers, serve_round).
 //
 // The fiber scheduler's invariants (match_scan_batch_claimed; Batch, FileScan, fiber_main):
 //  1. Ownership.  Live file i belongs to worker i % W for the whole scan; only that worker's thread ever switches
@@ -106,12 +106,44 @@ struct HostPool {
     }
 };
 
+// One batched K1 launch's descriptors: the per-file plans, the groups expanded from them on the device, and the tail
+// lanes; staged in pinned memory so that the upload is asynchronous (a pageable copy blocks the host while the device
+// idles).  `ev` guards the staging buffers' reuse by the next upload (batch.cpp stage_k1).
+struct K1Staging {
+    DevBuf plans, groups, lanes;
+    PinnedBuf h_plans, h_lanes;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    hipError_t ensure(size_t nplans, size_t ngroups, size_t nlanes) {
+        hipError_t e = hipSuccess;
+        if (pending && ((nplans + 1) * sizeof(K1Plan) > h_plans.cap || (nlanes + 1) * sizeof(K1Lane) > h_lanes.cap)) {
+            e = hipEventSynchronize(ev);  // a staging buffer that grows is freed: the upload that reads it first
+            pending = false;
+        }
+        if (e == hipSuccess) e = groups.ensure((ngroups + 1) * sizeof(K1Group));
+        if (e == hipSuccess) e = plans.ensure((nplans + 1) * sizeof(K1Plan));
+        if (e == hipSuccess) e = lanes.ensure((nlanes + 1) * sizeof(K1Lane));
+        if (e == hipSuccess) e = h_plans.ensure((nplans + 1) * sizeof(K1Plan));
+        if (e == hipSuccess) e = h_lanes.ensure((nlanes + 1) * sizeof(K1Lane));
+        return e;
+    }
+    ~K1Staging() {
+        if (ev) {
+            if (pending) (void)hipEventSynchronize(ev);
+            (void)hipEventDestroy(ev);
+        }
+        for (DevBuf* b : {&plans, &groups, &lanes}) b->release();
+        for (PinnedBuf* b : {&h_plans, &h_lanes}) b->release();
+    }
+};
+
 struct BatchState {
     HostPool pool;  // the events' copies (scan_batch)
-    // Generator batch
-    DevBuf g_groups, g_lanes, g_plans, k1_plans;  // K1 groups are expanded on the device from per-file plans
+    // the Generator batch's launch descriptors (uploaded on the context stream), and the Sender's speculation's
+    // (uploaded on the aux stream from the coordinator thread)
+    K1Staging gen_k1, spec_k1;
     // Sender batch: device
-    DevBuf slots, dslots, src_weak, src_strong, flags, haw, partials, bucket, first, k1_groups, k1_lanes;
+    DevBuf slots, dslots, src_weak, src_strong, flags, haw, partials, bucket, first;
     DevBuf d_probe;  // a large probe's descriptors (files, intervals, tiles, partial tiles) in device memory
     DevBuf fc_dev;   // FCHAIN rounds: the chains' gathered sums and bytes
     PinnedBuf h_fgw, h_fjobs, h_fout;  // ... their gather lists, chain jobs and chain outputs
@@ -125,15 +157,6 @@ struct BatchState {
     // file_abort[f] holds the scan's generation (written by the coordinator when f's resolver finishes)
     int* file_abort = nullptr;
     int64_t file_abort_cap = 0;
-    // Generator batch: its launch descriptors, staged in pinned memory so that the upload is asynchronous
-    // (a pageable copy blocks the host while the device idles); ev_gcopy guards the staging buffers' reuse
-    PinnedBuf h_ggroups, h_glanes;
-    hipEvent_t ev_gcopy = nullptr;
-    bool gcopy_pending = false;
-    // the same for the Sender's speculation launch (uploaded on the aux stream from the coordinator thread)
-    PinnedBuf h_sgroups, h_slanes;
-    hipEvent_t ev_scopy = nullptr;
-    bool scopy_pending = false;
     // the chain walk (options.h batch_chain): chunk indexes, descriptors, results and events (pinned), and the
     // speculation's flags kernel done on the aux stream (the walk reads the device flags and sums)
     DevBuf kslots;  // the chunk indexes' slots (8 B each), then one duplicate byte per chunk (launch_chunk_index)
@@ -161,26 +184,13 @@ struct BatchState {
     }
     ~BatchState() {
         if (file_abort) (void)hipFree(file_abort);
-        if (ev_gcopy) {
-            if (gcopy_pending) (void)hipEventSynchronize(ev_gcopy);
-            (void)hipEventDestroy(ev_gcopy);
-        }
-        if (ev_scopy) {
-            if (scopy_pending) (void)hipEventSynchronize(ev_scopy);
-            (void)hipEventDestroy(ev_scopy);
-        }
         for (hipEvent_t e : {ev_fk, ev_ch0, ev_ch1, ev_fa, ev_wa, ev_sync})
             if (e) (void)hipEventDestroy(e);
         kslots.release();
         for (PinnedBuf* b : {&h_kents, &h_chain, &h_chain_out, &h_chain_ev, &h_chain_help}) b->release();
         chain_help.release();
         chain_map.release();
-        h_ggroups.release();
-        h_glanes.release();
-        h_sgroups.release();
-        h_slanes.release();
-        for (DevBuf* b : {&d_probe, &fc_dev, &g_groups, &g_lanes, &g_plans, &k1_plans, &slots, &dslots, &src_weak, &src_strong, &flags, &haw, &partials, &bucket,
-                          &first, &k1_groups, &k1_lanes})
+        for (DevBuf* b : {&d_probe, &fc_dev, &slots, &dslots, &src_weak, &src_strong, &flags, &haw, &partials, &bucket, &first})
             b->release();
         for (PinnedBuf* b : {&h_weak, &h_strong, &h_aw, &h_as, &h_fl, &h_files, &h_hit, &h_win0, &h_bucket, &h_first,
                              &h_iv, &h_tiles, &h_segs, &h_ptiles, &h_req, &h_gw, &h_gb, &h_ow, &h_ob, &h_win, &h_copies,
@@ -306,19 +316,24 @@ class BatchBackend : public ScanBackend {
     int64_t probe_answer(const ProbeInterval* iv, int64_t count, const std::vector<int32_t>* keys);
 };
 
-struct FileScan {
-    int32_t job = 0;
+// A file's shape (d_src -- its alignment decides the K1 plan -- n, B, C, dl: the caller's) and its place in the
+// segment's buffers (the rest: SegmentLayout, batch.cpp)
+struct FileLayout {
     const uint8_t* d_src = nullptr;
-    const int32_t* d_weak = nullptr;
-    const uint8_t* d_strong = nullptr;
     int64_t n = 0, B = 0, na = 0, nf = 0;
     int64_t na_a = 0;  // two-phase chain walk: the windows of its prefix speculation (na: one phase)
     int64_t lane_b_bytes = 0;  // bytes of its phase-1 lane chunks (they poll no abort word: they always run)
-    const rsh_event* dev_ev = nullptr;  // a file the chain walk finished: its events, in the walk's pinned buffer
-    int64_t dev_n = 0;
     int32_t C = 0, dl = 0;
     uint32_t ns = 0;
     int64_t off_tw = 0, off_ts = 0, off_na = 0, off_as = 0, off_nf = 0, off_ns = 0, off_hit = 0, off_w0 = 0;
+};
+
+struct FileScan : FileLayout {
+    int32_t job = 0;
+    const int32_t* d_weak = nullptr;
+    const uint8_t* d_strong = nullptr;
+    const rsh_event* dev_ev = nullptr;  // a file the chain walk finished: its events, in the walk's pinned buffer
+    int64_t dev_n = 0;
     ChunkTable table;
     ResolveState rs;
     ResolveResult res;

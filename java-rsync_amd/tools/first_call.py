@@ -32,6 +32,8 @@ def main():
                          "clocks ramp under load after idle, which no library call controls")
     ap.add_argument("--trace-allocs", action="store_true", help="with --trace: scan_trace = 1 (every allocation)")
     ap.add_argument("--trim", action="store_true", help="config 4: after the reps, rsh_ctx_trim and one more rep")
+    ap.add_argument("--no-warm", action="store_true",
+                    help="option batch_warm = 0 before the context: the first batched scan allocates its own buffers")
     ap.add_argument("--host", action="store_true",
                     help="config 4 from host memory (rsh_block_sums_batch + rsh_match_scan_batch) instead of HBM")
     a = ap.parse_args()
@@ -40,6 +42,8 @@ def main():
     import rsync_hip as R
     import fullsize_golden as G
     out = {}
+    if a.no_warm:
+        R.set_option("batch_warm", 0)
     t = time.perf_counter()
     ctx = R.Context(0)
     if a.preheat > 0:  # after the context: its creation's own launches are part of the setup, not of the calls

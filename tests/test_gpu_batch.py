@@ -673,3 +673,171 @@ def test_generation_wrap(rsh_opt):
         P._sender_both(c, basis.tobytes(), src.tobytes(), B, dl)  # and a scan after it
     finally:
         c.close()
+
+
+# ---- scan_batch's decisions: each case asserts the trace line or stat that shows the decision it
+# ---- reaches, and compares every file with the oracle
+def _scan_against_oracle(ctx, files, stats=None):
+    """One batched scan of files [(basis, src, B, dl), bytes]: every file's status, events and counts against the
+    oracle's for that file alone (the tables are the oracle's Generator sums).  Returns the jobs."""
+    tabs, expect = [], []
+    for basis, src, B, dl in files:
+        oh = O.header(B, dl, len(basis))
+        ow, os_ = O.generator(basis, oh, SEED)
+        oev, _, olit, omat, _ = O.sender(src, oh, ow, os_, SEED)
+        tabs.append((np.asarray(ow, np.int32).tobytes(), np.asarray(os_, np.uint8).tobytes()))
+        expect.append(([tuple(e) for e in oev], olit, omat))
+    zeros = [0] * len(files)
+    d_w, woffs = _pack(ctx, [t[0] for t in tabs], zeros)
+    d_s, toffs = _pack(ctx, [t[1] for t in tabs], zeros)
+    d_src, soffs = _pack(ctx, [f[1] for f in files], zeros)
+    sj = (R.ScanJob * len(files))()
+    evs = []
+    for i, (basis, src, B, dl) in enumerate(files):
+        cap = len(expect[i][0]) + 8
+        ev = np.zeros(cap, R.EVENT_DTYPE)
+        evs.append(ev)
+        sj[i].d_src, sj[i].n, sj[i].h = d_src.ptr.value + soffs[i], len(src), R.header_make(B, dl, len(basis))
+        sj[i].d_weak, sj[i].d_strong = d_w.ptr.value + woffs[i], d_s.ptr.value + toffs[i]
+        sj[i].ev, sj[i].ev_cap = ev.ctypes.data, cap
+    rc = R.lib().rsh_match_scan_batch_device(ctx.handle, sj, len(files), SEED_NP.ctypes.data,
+                                             ctypes.byref(stats) if stats is not None else None)
+    assert rc == 0, (rc, R.lib().rsh_last_error())
+    for i, (basis, src, B, dl) in enumerate(files):
+        oev, olit, omat = expect[i]
+        assert sj[i].status == 0, f"file {i}"
+        assert R.events_as_tuples(evs[i][:sj[i].n_ev], B) == oev, f"file {i}: B={B} n={len(src)}"
+        assert (sj[i].literal, sj[i].matched) == (olit, omat), f"file {i}"
+    return sj
+
+
+def _batch_lines(err):
+    return [ln for ln in err.splitlines() if ln.startswith("[rsh-batch]")]
+
+
+@pytest.mark.parametrize("edit", ["twin", "twin_one_identical", "insert"])
+def test_batch_two_phase_rest_skipped_or_launched(ctx, edit, rsh_opt, capfd):
+    """Two phases (batch_chain_prefix = 8 windows of 64), every file edited inside its first 8 blocks.
+    twin: one block replaced by a weak twin (its weak sum, another digest) poisons the walk there with a digest no
+    chunk carries: the walk closes the file (CHAIN_DONE) inside the prefix, no walk returns CHAIN_MORE, and the rest of
+    the speculation, its flags and phase 1 are skipped; what waits on the speculation's events finds them complete
+    (speculation_aborted == 0).  twin_one_identical: the identical file's walk reaches the prefix's end, the rest is
+    launched.  insert: one byte inserted; each walk stops unpoisoned at the first unaligned position after a match
+    (CHAIN_WHY_PHASE) and its resolver finds the later blocks one byte on, by probes anchored on the speculation's
+    sums past the prefix: the rest is launched for them (the library before this case skipped it, and file 0's
+    events ended in literals from byte 32769 on where the oracle has the MATCH of chunk 8)."""
+    rsh_opt("batch_chain_prefix", 8)
+    rsh_opt("scan_trace", 2)
+    B, dl = 4096, 3
+    rng = random.Random(88)
+    files = []
+    for i in range(4):
+        basis = np.frombuffer(O.splitmix(64 * B + 100 * i, 0xD0C0 + i).tobytes(), np.uint8) & 0x7F
+        src = basis.copy()
+        if edit == "insert":
+            x = (1 + i) * B + 77 * i + 5
+            src = np.concatenate([basis[:x], np.full(1, 0x5A, np.uint8), basis[x:]])
+        elif not (edit == "twin_one_identical" and i == 2):
+            k = 1 + i
+            src[k * B:(k + 1) * B] = _weak_twin(basis[k * B:(k + 1) * B], rng)
+        files.append((basis.tobytes(), src.tobytes(), B, dl))
+    st = R.ScanStats()
+    capfd.readouterr()
+    _scan_against_oracle(ctx, files, st)
+    lines = _batch_lines(capfd.readouterr().err)
+    two = [ln for ln in lines if "two-phase speculation:" in ln]
+    assert len(two) == 1, lines
+    assert ("(skipped" in two[0]) == (edit == "twin"), two
+    assert st.speculation_aborted == 0
+
+
+@pytest.mark.parametrize("why", ["over_budget", "no_wide_file"])
+def test_batch_two_phase_without_hit_map(ctx, why, rsh_opt, capfd):
+    """Two phases with helpers asked for (chain_helpers = 3) and no hit map all the same: its words would not fit option
+    chain_map_bytes (64 bytes here), or no file has wide tiles (B = 700 is no multiple of 32).  The walks search every
+    tile themselves -- `(0 from the hit map)` -- over sources with every other block replaced."""
+    rsh_opt("batch_chain_prefix", 16)
+    rsh_opt("chain_helpers", 3)
+    rsh_opt("scan_trace", 2)
+    if why == "over_budget":
+        rsh_opt("chain_map_bytes", 64)
+    B, files = (1024 if why == "over_budget" else 700), []
+    for i in range(3):
+        nb = 48 * B + 33 * i
+        basis = np.frombuffer(O.splitmix(nb, 0x0FF0 + i).tobytes(), np.uint8)
+        src = basis.copy()
+        src[:48 * B].reshape(-1, B)[1::2] = np.frombuffer(O.splitmix(24 * B, 0x1FF0 + i).tobytes(), np.uint8).reshape(-1, B)
+        files.append((basis.tobytes(), src.tobytes(), B, 3))
+    capfd.readouterr()
+    _scan_against_oracle(ctx, files)
+    lines = _batch_lines(capfd.readouterr().err)
+    assert sum("two-phase speculation:" in ln for ln in lines) == 1, lines
+    walks = [ln for ln in lines if "chain walks done" in ln]
+    assert len(walks) == 1 and "(0 from the hit map)" in walks[0], lines
+
+
+@pytest.mark.parametrize("form", ["unrelated", "identical"])
+def test_batch_tentative_launch_stopped_or_kept(ctx, form, rsh_opt, capfd):
+    """Without the chain walk (batch_chain = 0) the speculation's K1 is launched before the lead check.  No file's
+    first windows carry its table's sums (unrelated bases): nwait == 0, the launch is stopped, and these files -- no
+    longer than 10 blocks, so each is one probe and no flush -- finish before the deferred launch (kDeferRounds = 2):
+    no speculation, speculation_aborted == 2.  Identical files all wait for it: it is kept and lands (== 0)."""
+    rsh_opt("batch_chain", 0)
+    rsh_opt("scan_trace", 2)
+    files = []
+    for i, B in enumerate([512, 700, 4096]):
+        basis = O.splitmix(6 * B + 31 * i, 0x7E57 + i).tobytes()
+        src = basis if form == "identical" else O.splitmix(5 * B + 17 * i, 0xFACE + i).tobytes()
+        files.append((basis, src, B, 2 + i))
+    st = R.ScanStats()
+    capfd.readouterr()
+    _scan_against_oracle(ctx, files, st)
+    lines = _batch_lines(capfd.readouterr().err)
+    want = "lead check: %d of 3 files wait for the speculation" % (3 if form == "identical" else 0)
+    assert sum(want in ln for ln in lines) == 1, lines
+    assert st.speculation_aborted == (0 if form == "identical" else 2)
+
+
+def test_batch_call_of_257_files_is_split(ctx, rsh_opt, capfd):
+    """More files than kMaxLive (256) in one call: two parts (256 files, then 1), each its own scan -- one summary line
+    per part.  Files of two or three blocks at B = 512, identical and edited ones mixed; every status and every
+    file's events."""
+    rsh_opt("scan_trace", 2)
+    rng = random.Random(257)
+    B, files = 512, []
+    for i in range(257):
+        nb = rng.choice([2, 3]) * B + rng.randrange(0, B)
+        basis = O.splitmix(nb, 0x257000 + i).tobytes()
+        src = basis
+        if i % 3 == 1:
+            x = rng.randrange(1, nb - 1)
+            src = basis[:x] + bytes([basis[x] ^ 0x40]) + basis[x + 1:]
+        elif i % 3 == 2:
+            x = rng.randrange(0, nb)
+            src = basis[:x] + O.splitmix(rng.randrange(1, 40), i).tobytes() + basis[x:]
+        files.append((basis, src, B, rng.choice([2, 3, 4])))
+    capfd.readouterr()
+    _scan_against_oracle(ctx, files)
+    lines = _batch_lines(capfd.readouterr().err)
+    parts = [ln.split("]")[1].split(":")[0].strip() for ln in lines if "tables+hashes ready" in ln]
+    assert parts == ["256 files", "1 files"], parts
+
+
+def test_batch_events_copied_on_the_pool(ctx, rsh_opt):
+    """More than 1 MiB of events in one call (32-byte events) go back to the callers' buffers on the context's HostPool,
+    several files per thread: the only path where threads other than the caller's write the callers' buffers.
+    48 files of 1024 blocks at B = 512 with every other block replaced: ~1024 events each unless a false weak hit
+    poisons the walk early (about one file in 16 at this size; three files of 6 MiB gave 4044 events in all, every walk
+    poisoned within its first MiB).  host_cores = 4 gives the call four copy threads on any machine.  Every file's
+    events against the oracle."""
+    rsh_opt("host_cores", 4)
+    B, nblk, files = 512, 1024, []
+    for i in range(48):
+        nb = nblk * B + 10 * i
+        basis = np.frombuffer(O.splitmix(nb, 0xC0B100 + i).tobytes(), np.uint8)
+        other = np.frombuffer(O.splitmix(nb, 0xC0B900 + i).tobytes(), np.uint8)
+        src = basis.copy()
+        src[:nblk * B].reshape(-1, B)[1::2] = other[:nblk * B].reshape(-1, B)[1::2]
+        files.append((basis.tobytes(), src.tobytes(), B, 4))
+    sj = _scan_against_oracle(ctx, files)
+    assert sum(sj[i].n_ev for i in range(len(files))) * R.EVENT_DTYPE.itemsize > 1 << 20

@@ -77,3 +77,22 @@ def test_batch_warm_presizes_at_context_creation():
         assert r.returncode == 0, r.stderr[-3000:]
         free.append(int(r.stdout.strip().splitlines()[-1]))
     assert free[1] - free[0] >= 150 << 20, free
+
+
+def test_first_segment_scan_allocates_nothing():
+    """The batched scan sizes its buffers in one place (batch.cpp SegmentLayout), which rsh_ctx_create's warm-up calls
+    with config 4's shard: a fresh context's first segment scan within that shape -- four of its 128 MiB files here --
+    allocates nothing.  first_call.py --trace-allocs sets scan_trace = 1 around that scan alone, which prints one line
+    per device or pinned allocation.  The control: the same run with the warm-up off (--no-warm: batch_warm = 0) must
+    print such lines, so the empty list is neither tracing left off nor a changed line format."""
+    import re
+
+    def allocs(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "java-rsync_amd", "tools", "first_call.py"), "--only", "4",
+                            "--files", "4", "--reps", "1", "--trace", "--trace-allocs", *extra], capture_output=True,
+                           text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert "[rsh-batch] 4 files: enqueued" in r.stderr, r.stderr[-3000:]  # the scan was traced
+        return [ln for ln in r.stderr.splitlines() if re.match(r"\[rsh\] (dev_alloc|pin_alloc)\b", ln)]
+    assert allocs("--no-warm") != []
+    assert allocs() == []
