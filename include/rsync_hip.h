@@ -316,6 +316,77 @@ typedef struct {
 int rsh_match_scan_batch(rsh_ctx* ctx, rsh_scan_batch_job* jobs, int32_t njobs, const uint8_t seed[4],
                          rsh_scan_stats* stats);
 
+/* ---- the checksum table in wire form ----
+ * The bytes the Generator writes for one file and the Sender reads: the 16 header bytes of
+ * Connection.sendChecksumHeader (Connection.java:40-45), then chunk_count records of 4 + digest_length bytes, the
+ * little-endian weak sum and the digest bytes (Generator.java:888-895; read back by Sender.receiveChecksumsFor,
+ * Sender.java:758-767).  rsh_generator_bytes above is the definition.  The device forms convert between these bytes
+ * and the two arrays in HBM that the block sums write and the scans read (sums_frame_kernel / sums_unframe_kernel), for
+ * every digest_length >= 0 (a peer may send more than the Generator's 16). */
+/* 16 + chunk_count * (4 + digest_length); RSH_E_INVAL for a negative count or length.  Pure host. */
+int64_t rsh_sums_wire_size(const rsh_header* h);
+/* Connection.receiveChecksumHeader (Connection.java:28-38): the four ints parsed, then the 4-arg validation:
+ * RSH_E_PROTOCOL exactly where rsh_header_validate gives it (*out is then untouched).  Pure host. */
+int rsh_header_from_wire(const uint8_t wire[16], rsh_header* out);
+/* Header + table of the sums in HBM (d_weak, d_strong) into the host buffer `out` (any memory; staged through the
+ * library's pinned buffer).  h is the Generator's own header (any block length its 3-arg constructor makes);
+ * RSH_E_INVAL for a negative count or length, RSH_E_NOSPACE when cap is short of rsh_sums_wire_size. */
+int rsh_sums_frame_device(rsh_ctx* ctx, const rsh_header* h, const void* d_weak, const void* d_strong, uint8_t* out,
+                          int64_t cap);
+/* The records as received (host memory, no header; len must equal chunk_count * (4 + digest_length), else
+ * RSH_E_INVAL) into d_weak and d_strong, which rsh_match_scan_device and rsh_match_scan_batch_device then take. */
+int rsh_sums_unframe_device(rsh_ctx* ctx, const rsh_header* h, const uint8_t* records, int64_t len, void* d_weak,
+                            void* d_strong);
+
+/* ---- a segment's files from host memory, in channel bytes ----
+ * The two segment calls above with the reference's channel bytes on both sides, so that the Java side moves each
+ * file's table and reply with one bulk put / get instead of a loop per chunk or per token.
+ * Generator: `out` receives header + table exactly as Generator.sendItemizeAndChecksums writes them (a pass's tables
+ * are framed by one kernel launch; an empty file's 16 header bytes and the table of a file larger than a pass come
+ * from the host).  Per-file statuses as rsh_block_sums_batch, plus RSH_E_NOSPACE (out_len = the size needed) for a
+ * short out_cap, which fails that file only. */
+typedef struct {
+    const rsh_piece* pieces; /* the basis file */
+    int32_t npieces;
+    int32_t status;          /* out */
+    rsh_header h;            /* as rsh_block_batch_job */
+    uint8_t* out;            /* host, caller-owned: out_cap bytes */
+    int64_t out_cap;
+    int64_t out_len;         /* out: rsh_sums_wire_size(&h) */
+} rsh_block_wire_job;
+int rsh_block_sums_batch_wire(rsh_ctx* ctx, rsh_block_wire_job* jobs, int32_t njobs, const uint8_t seed[4]);
+/* Sender: one transfer request and its whole reply.  `table` holds the file's records as they came off the channel
+ * (after the header, which the caller parsed with rsh_header_from_wire); they go to HBM raw and are unframed there.
+ * status, ev, n_ev, literal, matched and file_md5 are rsh_match_scan_batch's (a short ev_cap is RSH_E_NOSPACE in
+ * status, and then there is no stream; table_len other than chunk_count * (4 + digest_length) is RSH_E_INVAL for that
+ * file only).  `out` receives the bytes of rsh_tokens_write: each pass's streams are framed from the sources the pass
+ * holds in HBM, before the next pass replaces them; a new file (block_length 0) and an empty source are framed from
+ * the pieces.  out_status: RSH_OK when the stream is in `out`; RSH_E_NOSPACE (out_len = the size needed) when out_cap
+ * is short; RSH_E_NOSOURCE for a file larger than a pass, scanned tiled; the status's code when the scan failed.  With
+ * NOSPACE and NOSOURCE the events are valid and the caller replays them itself.
+ * A caller that must flip md5[0] after a read error (Sender.java:1136-1143) overwrites the last 16 bytes of `out`. */
+typedef struct {
+    const rsh_piece* pieces; /* the source file */
+    int32_t npieces;
+    int32_t status;          /* out */
+    rsh_header h;            /* the received header (validated as by rsh_match_scan) */
+    const uint8_t* table;    /* host: the received records */
+    int64_t table_len;
+    rsh_event* ev;           /* host, caller-owned: ev_cap entries */
+    int64_t ev_cap;
+    int64_t n_ev;            /* out */
+    int64_t literal;         /* out */
+    int64_t matched;         /* out */
+    uint8_t file_md5[16];    /* out */
+    uint8_t* out;            /* host, caller-owned: out_cap bytes */
+    int64_t out_cap;
+    int64_t out_len;         /* out: the stream's size */
+    int32_t out_status;      /* out */
+    int32_t reserved;
+} rsh_send_job;
+int rsh_match_scan_batch_wire(rsh_ctx* ctx, rsh_send_job* jobs, int32_t njobs, const uint8_t seed[4],
+                              rsh_scan_stats* stats);
+
 /* Whole-file MD5s of many files (pure host; no context): md5[16] of each job = MD5 of its pieces'
  * concatenation.  Independent files run side by side, up to 16 per core (AVX-512; 8 with AVX2), on `threads`
  * threads (0 = the process's cores, cgroup quota included). */
@@ -401,6 +472,11 @@ int rsh_block_sums_batch_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_block_bat
                                const uint8_t seed[4]);
 int rsh_match_scan_batch_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_scan_batch_job* jobs, int32_t njobs,
                                const uint8_t seed[4], rsh_scan_stats* stats);
+/* (the wire forms: the same split by the pieces' bytes) */
+int rsh_block_sums_batch_wire_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_block_wire_job* jobs, int32_t njobs,
+                                    const uint8_t seed[4]);
+int rsh_match_scan_batch_wire_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_send_job* jobs, int32_t njobs,
+                                    const uint8_t seed[4], rsh_scan_stats* stats);
 /* (the Receiver's files are split by max(tokens_len, replica bytes): about the bytes each rebuilds) */
 int rsh_receiver_combine_batch_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_combine_job* jobs, int32_t njobs);
 /* The split (pure host): part_out[f] = the part (context) file f goes to.  Longest first by bytes (equal sizes in

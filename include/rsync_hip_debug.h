@@ -7,7 +7,7 @@
  * Tests force rare paths with them; a few are tunables: k1_gather, k1_shift,
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
- * fault_inject, tokens_span, tokens_piece.
+ * fault_inject, tokens_span, tokens_piece, sums_piece.
  */
 #ifndef RSYNC_HIP_DEBUG_H
 #define RSYNC_HIP_DEBUG_H
@@ -28,7 +28,8 @@ void rsh_debug_reset_options(void);
 
 /* The duration of a K1 from its own dispatch timestamps (HIP events recorded by the launch, hipExtLaunchKernelGGL):
  * which 0 = the last rsh_block_sums_device's K1 (the Generator), 1 = the last single-file scan's aligned speculation
- * when it ran to completion.  *ms = -1 when that launch was not timed (a shape whose kernel takes no events). */
+ * when it ran to completion, 2 = the last sums_frame_kernel / sums_unframe_kernel launch (HIP events around it).
+ * *ms = -1 when that launch was not timed (a shape whose kernel takes no events). */
 int rsh_debug_kernel_ms(rsh_ctx* ctx, int32_t which, double* ms);
 
 /* The context's launch generation (the abort and hit-map words' values): *gen its current value; set >= 0 (at most
@@ -62,6 +63,14 @@ int rsh_debug_multi_selftest(const int64_t* bytes, int32_t njobs, int32_t nparts
 int rsh_debug_tokens_selftest(const uint8_t* src, int64_t n, const rsh_event* ev, int64_t n_ev,
                               const uint8_t file_md5[16], int64_t from, uint8_t* out, int64_t len, int64_t span,
                               int64_t* n_desc);
+
+/* The planner and kernels of the wire-form table (rsh_sums_frame_device / rsh_sums_unframe_device) without a device:
+ * plans the spans at `span` bytes per descriptor (0: the production size) and executes them with a host stand-in that
+ * runs the kernels' block split and per-byte arithmetic (sums_frame.h) over host pointers.  unframe == 0: weak, strong
+ * -> `wire` (header + records; len: its capacity, RSH_E_NOSPACE when short); unframe != 0: `wire` (records only, len
+ * bytes: RSH_E_INVAL unless chunk_count * (4 + digest_length)) -> weak, strong.  *n_desc: the descriptor count. */
+int rsh_debug_sums_selftest(int32_t unframe, const rsh_header* h, int32_t* weak, uint8_t* strong, uint8_t* wire,
+                            int64_t len, int64_t span, int64_t* n_desc);
 
 #ifdef __cplusplus
 }

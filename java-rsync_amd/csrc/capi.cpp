@@ -204,10 +204,10 @@ int rsh_ctx_trim(rsh_ctx* ctx) {
     RSH_HIP(hipSetDevice(ctx->device));
     for (hipStream_t st : {ctx->stream, ctx->aux, ctx->phase}) RSH_HIP(hipStreamSynchronize(st));
     for (DevBuf* b : {&ctx->data, &ctx->weak, &ctx->strong, &ctx->seg_data, &ctx->seg_tab, &ctx->rcv[0], &ctx->rcv[1],
-                      &ctx->rcv_ops[0], &ctx->rcv_ops[1], &ctx->out})
+                      &ctx->rcv_ops[0], &ctx->rcv_ops[1], &ctx->out, &ctx->sums_raw})
         b->release();
     for (PinnedBuf* b : {&ctx->h_stage, &ctx->h_rcv_ops[0], &ctx->h_rcv_ops[1], &ctx->h_out, &ctx->h_tok, &ctx->h_tokd[0],
-                         &ctx->h_tokd[1]})
+                         &ctx->h_tokd[1], &ctx->h_sums, &ctx->h_sumsd})
         b->release();
     if (ctx->h_win.cap > (1u << 20)) ctx->h_win.release();  // (a Receiver pass's pieces; the scan's windows are small)
     // The batched scan's state stays: its chunk index, hit map, descriptors, pinned event and
@@ -541,14 +541,16 @@ void rsh_debug_reset_options(void) {
 }
 
 int rsh_debug_kernel_ms(rsh_ctx* ctx, int32_t which, double* ms) {
-    if (!ctx || !ms || which < 0 || which > 1) return RSH_E_INVAL;
+    if (!ctx || !ms || which < 0 || which > 2) return RSH_E_INVAL;
     *ms = -1.0;
-    const bool timed = which == 0 ? ctx->gen_timed : ctx->spec_timed;
+    const bool timed = which == 0 ? ctx->gen_timed : which == 1 ? ctx->spec_timed : ctx->sums_timed;
     if (!timed) return RSH_OK;
+    const hipEvent_t a = which == 0 ? ctx->ev_gen_a : which == 1 ? ctx->ev_k1a : ctx->ev_sums_a;
+    const hipEvent_t b = which == 0 ? ctx->ev_gen_b : which == 1 ? ctx->ev_k1b : ctx->ev_sums_b;
     RSH_HIP(hipSetDevice(ctx->device));
-    RSH_HIP(hipEventSynchronize(which == 0 ? ctx->ev_gen_b : ctx->ev_k1b));
+    RSH_HIP(hipEventSynchronize(b));
     float f = 0.f;
-    RSH_HIP(hipEventElapsedTime(&f, which == 0 ? ctx->ev_gen_a : ctx->ev_k1a, which == 0 ? ctx->ev_gen_b : ctx->ev_k1b));
+    RSH_HIP(hipEventElapsedTime(&f, a, b));
     *ms = f;
     return RSH_OK;
 }

@@ -62,6 +62,27 @@ hipError_t batch_warm(rsh_ctx* c, int32_t nfiles, int64_t n, int64_t B, int32_t 
 int block_sums_batch_claimed(rsh_ctx* ctx, const rsh_block_job* jobs, int32_t njobs, const uint8_t seed[4]);
 int match_scan_batch_claimed(rsh_ctx* ctx, rsh_scan_job* jobs, int32_t njobs, const uint8_t seed[4],
                              rsh_scan_stats* stats);
+// tokens.cpp: rsh_tokens_write_batch_device for a caller that holds the context's claim
+int tokens_write_batch_claimed(rsh_ctx* ctx, rsh_token_job* jobs, int32_t njobs);
+// sums_wire.cpp, for a caller that holds the context's claim.  Frame: every file's whole wire stream (header + table
+// of the sums in HBM) into its host buffer `out`, the files' streams sharing the launches; returns after the bytes are
+// there.  Unframe: every file's record bytes (host) into its two arrays in HBM; returns after the records were read.
+struct SumsFrameWork {
+    rsh_header h;
+    const void* d_weak;
+    const void* d_strong;
+    uint8_t* out;
+};
+int sums_frame_files(rsh_ctx* ctx, const SumsFrameWork* w, size_t n);
+struct SumsUnframeWork {
+    rsh_header h;
+    const uint8_t* records;
+    void* d_weak;
+    void* d_strong;
+};
+int sums_unframe_files(rsh_ctx* ctx, const SumsUnframeWork* w, size_t n);
+// ... and the same on the host, record by record (a file scanned tiled keeps its table in host memory)
+void sums_unframe_host(const rsh_header& h, const uint8_t* records, int32_t* weak, uint8_t* strong);
 }  // namespace rsh
 
 namespace rshi {
@@ -248,6 +269,12 @@ struct rsh_ctx {
     // with its span descriptors and the event that marks its launch done (tokens.cpp)
     PinnedBuf h_tok, h_tokd[2];
     hipEvent_t ev_tok[2] = {nullptr, nullptr};
+    // the checksum table in wire form (sums_wire.cpp): one pinned staging piece of table bytes, its span descriptors,
+    // and the record bytes of a piece in HBM (the unframe kernel's source)
+    PinnedBuf h_sums, h_sumsd;
+    DevBuf sums_raw;
+    hipEvent_t ev_sums_a = nullptr, ev_sums_b = nullptr;  // timing: the last sums kernel (rsh_debug_kernel_ms)
+    bool sums_timed = false;
     std::atomic<bool> busy{false};   // the staging buffers and last_ev serve one call at a time
     rsh::BatchState* batch = nullptr;  // buffers of the batched (multi-file) entry points, on first use
     ~rsh_ctx() {
@@ -255,12 +282,12 @@ struct rsh_ctx {
         for (DevBuf* b : {&data, &weak, &strong, &src_weak, &src_strong, &flags, &ph_weak[0], &ph_strong[0],
                           &ph_weak[1], &ph_strong[1], &slots, &dslots,
                           &out, &first, &haw, &partials, &bucket, &seg_data, &seg_tab,
-                          &rcv[0], &rcv[1], &rcv_ops[0], &rcv_ops[1], &prep_dev, &fc_dev})
+                          &rcv[0], &rcv[1], &rcv_ops[0], &rcv_ops[1], &prep_dev, &fc_dev, &sums_raw})
             b->release();
         for (PinnedBuf* b : {&h_weak, &h_strong, &h_aw, &h_as, &h_fl, &h_pw[0], &h_ps[0], &h_pw[1], &h_ps[1], &h_lead, &h_pos, &h_out, &h_iv,
                              &h_tiles, &h_keys, &h_first, &h_win, &h_ptiles, &h_psegs, &h_hit, &h_win0, &h_pend, &h_bucket, &h_files,
                              &h_stage, &h_rcv_ops[0], &h_rcv_ops[1], &h_prep, &h_stamps, &h_fgw, &h_fjobs, &h_fout,
-                             &h_tok, &h_tokd[0], &h_tokd[1]})
+                             &h_tok, &h_tokd[0], &h_tokd[1], &h_sums, &h_sumsd})
             b->release();
         if (abort_word) (void)hipFree(abort_word);
         if (ev_in) (void)hipEventDestroy(ev_in);
@@ -270,7 +297,7 @@ struct rsh_ctx {
             if (e) (void)hipEventDestroy(e);
         if (ev_flags) (void)hipEventDestroy(ev_flags);
         if (ev_prep) (void)hipEventDestroy(ev_prep);
-        for (hipEvent_t e : {ev_k1a, ev_k1b, ev_gen_a, ev_gen_b, ev_rs_tail, ev_tok[0], ev_tok[1]})
+        for (hipEvent_t e : {ev_k1a, ev_k1b, ev_gen_a, ev_gen_b, ev_rs_tail, ev_tok[0], ev_tok[1], ev_sums_a, ev_sums_b})
             if (e) (void)hipEventDestroy(e);
         if (aux) (void)hipStreamDestroy(aux);
         if (phase) (void)hipStreamDestroy(phase);

@@ -337,6 +337,12 @@ hipError_t launch_gather_ops_variant(int v, const GatherOp* ops, uint32_t n, hip
 struct TokSpan;
 hipError_t launch_token_frame(const TokSpan* spans, uint32_t n, uint32_t max_len, bool dst_on_host, hipStream_t s);
 hipError_t launch_warm_tokens(hipStream_t s);
+// The checksum table between SoA and wire form (device_sums.hip, sums_frame.h): spans in device or pinned host
+// memory; max_len: the longest span's bytes.
+struct SumsSpan;
+hipError_t launch_sums_frame(const SumsSpan* spans, uint32_t n, uint32_t max_len, hipStream_t s);
+hipError_t launch_sums_unframe(const SumsSpan* spans, uint32_t n, uint32_t max_len, hipStream_t s);
+hipError_t launch_warm_sums(hipStream_t s);
 // Probe hashes of many files (slots cleared by the caller): keys[i] into slots/mask.
 struct TableEnt {
     unsigned long long* slots;

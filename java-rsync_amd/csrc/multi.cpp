@@ -157,6 +157,43 @@ int rsh_match_scan_batch_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_scan_batc
     return rc;
 }
 
+// The wire forms (segment.cpp): split by the pieces' bytes as the two above; `out` and `table` are the caller's
+// pointers, so the job copies carry them.
+int rsh_block_sums_batch_wire_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_block_wire_job* jobs, int32_t njobs,
+                                    const uint8_t seed[4]) {
+    if (!ctxs_ok(ctxs, nctx) || !seed || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
+    if (nctx == 1) return rsh_block_sums_batch_wire(ctxs[0], jobs, njobs, seed);
+    std::vector<int64_t> bytes((size_t)njobs);
+    for (int32_t f = 0; f < njobs; ++f) bytes[(size_t)f] = pieces_bytes(jobs[f].pieces, jobs[f].npieces);
+    return run_members(
+        nctx, jobs, njobs, bytes,
+        [&](int32_t p, rsh_block_wire_job* sub, int32_t n) {
+            return member_call(p, [&] { return rsh_block_sums_batch_wire(ctxs[p], sub, n, seed); });
+        },
+        [](const rsh_block_wire_job& j) { return j.status; });
+}
+
+int rsh_match_scan_batch_wire_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_send_job* jobs, int32_t njobs,
+                                    const uint8_t seed[4], rsh_scan_stats* stats) {
+    if (!ctxs_ok(ctxs, nctx) || !seed || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
+    if (nctx == 1) return rsh_match_scan_batch_wire(ctxs[0], jobs, njobs, seed, stats);
+    if (stats) *stats = rsh_scan_stats{};
+    std::vector<int64_t> bytes((size_t)njobs);
+    for (int32_t f = 0; f < njobs; ++f) bytes[(size_t)f] = pieces_bytes(jobs[f].pieces, jobs[f].npieces);
+    std::vector<rsh_scan_stats> ps((size_t)nctx);
+    const int rc = run_members(
+        nctx, jobs, njobs, bytes,
+        [&](int32_t p, rsh_send_job* sub, int32_t n) {
+            return member_call(p, [&] {
+                return rsh_match_scan_batch_wire(ctxs[p], sub, n, seed, stats ? &ps[(size_t)p] : nullptr);
+            });
+        },
+        [](const rsh_send_job& j) { return j.status; });
+    if (stats)
+        for (const rsh_scan_stats& s : ps) add_scan_stats(stats, s);
+    return rc;
+}
+
 int rsh_receiver_combine_batch_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_combine_job* jobs, int32_t njobs) {
     if (!ctxs_ok(ctxs, nctx) || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
     if (nctx == 1) return rsh_receiver_combine_batch(ctxs[0], jobs, njobs);

@@ -164,6 +164,96 @@ int block_sums_passes(rsh_ctx* ctx, rsh_block_batch_job* jobs, const std::vector
     return RSH_OK;
 }
 
+// rsh_block_sums_batch_wire's device work, as block_sums_passes: after a pass's K1 one sums_frame_kernel launch frames
+// every file's header + table into pinned staging, from where they go to each `out`.
+int block_wire_passes(rsh_ctx* ctx, rsh_block_wire_job* jobs, const std::vector<int32_t>& run,
+                      const std::vector<int64_t>& n, const uint8_t seed[4], std::vector<char>& done) {
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    for (const Pass& pass : plan_passes(run, n)) {
+        if (pass.alone) {  // larger than a pass: tile by tile (pieces.cpp), its table framed on the host
+            rsh_block_wire_job& j = jobs[pass.files[0]];
+            const size_t C = (size_t)j.h.chunk_count, dl = (size_t)j.h.digest_length;
+            std::vector<int32_t> weak(C + 1);
+            std::vector<uint8_t> strong(C * dl + 1);
+            j.status = rsh::block_sums_pieces_claimed(ctx, j.pieces, j.npieces, n[(size_t)pass.files[0]], &j.h, seed,
+                                                      weak.data(), strong.data());
+            if (j.status == RSH_OK && rsh_generator_bytes(&j.h, weak.data(), strong.data(), j.out, j.out_cap) != j.out_len)
+                j.status = RSH_E_INVAL;
+            done[(size_t)pass.files[0]] = 1;
+            if (j.status != RSH_OK) return j.status;
+            continue;
+        }
+        int64_t data_bytes = 0, sum_bytes = 0;
+        for (int32_t f : pass.files) {
+            data_bytes += align_up(n[(size_t)f]);
+            sum_bytes += align_up(4 * (int64_t)jobs[f].h.chunk_count) +
+                         align_up((int64_t)jobs[f].h.chunk_count * jobs[f].h.digest_length);
+        }
+        if (fail_alloc() || ctx->seg_data.ensure((size_t)data_bytes + kAlign) != hipSuccess ||
+            ctx->seg_tab.ensure((size_t)sum_bytes + kAlign) != hipSuccess) {
+            snprintf(g_last_err, sizeof(g_last_err), "segment pass of %lld bytes: device memory (segment.cpp)",
+                     (long long)(data_bytes + sum_bytes));
+            return RSH_E_NOMEM;
+        }
+        std::vector<rsh_block_job> bj;
+        std::vector<rsh::SumsFrameWork> fw;
+        int64_t doff = 0, soff = 0;
+        for (int32_t f : pass.files) {
+            const rsh_block_wire_job& j = jobs[f];
+            uint8_t* d = ctx->seg_data.as<uint8_t>() + doff;
+            uint8_t* w = ctx->seg_tab.as<uint8_t>() + soff;
+            uint8_t* s = w + align_up(4 * (int64_t)j.h.chunk_count);
+            RSH_HIP(fail_copy(copy_pieces(j.pieces, j.npieces, d, ctx->stream)));
+            bj.push_back(rsh_block_job{d, n[(size_t)f], j.h, w, s});
+            fw.push_back(rsh::SumsFrameWork{j.h, w, s, j.out});
+            doff += align_up(n[(size_t)f]);
+            soff += align_up(4 * (int64_t)j.h.chunk_count) + align_up((int64_t)j.h.chunk_count * j.h.digest_length);
+        }
+        int rc = rsh::block_sums_batch_claimed(ctx, bj.data(), (int32_t)bj.size(), seed);
+        if (rc == RSH_OK) rc = rsh::sums_frame_files(ctx, fw.data(), fw.size());
+        if (rc != RSH_OK) return rc;
+        for (int32_t f : pass.files) done[(size_t)f] = 1;
+    }
+    return RSH_OK;
+}
+
+// Bytes [off, off + len) of the pieces' concatenation.
+void copy_range(const rsh_piece* p, int32_t np, int64_t off, int64_t len, uint8_t* dst) {
+    for (int32_t i = 0; i < np && len > 0; ++i) {
+        if (off >= p[i].len) {
+            off -= p[i].len;
+            continue;
+        }
+        const int64_t k = std::min(len, p[i].len - off);
+        memcpy(dst, p[i].data + off, (size_t)k);
+        dst += k;
+        len -= k;
+        off = 0;
+    }
+}
+
+// rsh_tokens_write's bytes before the trailer for a source held as pieces (a new file's literals; an empty source has
+// no events at all).
+void tokens_from_pieces(const rsh_piece* p, int32_t np, const rsh_event* ev, int64_t n_ev, uint8_t* o) {
+    for (int64_t i = 0; i < n_ev; ++i) {
+        if (ev[i].kind == RSH_EV_LITERAL) {  // Sender.sendDataFrom (Sender.java:794-809)
+            for (int64_t cur = ev[i].offset, end = ev[i].offset + ev[i].length; cur < end;) {
+                const int64_t len = std::min<int64_t>(kChunkSize, end - cur);
+                for (int b = 0; b < 4; ++b) *o++ = (uint8_t)((uint32_t)len >> (8 * b));
+                copy_range(p, np, cur, len, o);
+                o += len;
+                cur += len;
+            }
+        } else {
+            for (int32_t k = 0; k < ev[i].count; ++k) {
+                const uint32_t v = 0u - ((uint32_t)ev[i].index + (uint32_t)k + 1u);
+                for (int b = 0; b < 4; ++b) *o++ = (uint8_t)(v >> (8 * b));
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -384,6 +474,259 @@ int rsh_match_scan_batch(rsh_ctx* ctx, rsh_scan_batch_job* jobs, int32_t njobs, 
     md5_thread.join();
     if (rc != RSH_OK) (void)hipStreamSynchronize(ctx->stream);  // no copy from the caller's buffers outlives the call
     for (size_t k = 0; k < ok.size(); ++k) memcpy(jobs[ok[k]].file_md5, md5.data() + 16 * k, 16);
+    if (rc != RSH_OK) return fail_unfinished(rc);
+    for (int32_t i = 0; i < njobs; ++i)
+        if (jobs[i].status != RSH_OK) return jobs[i].status;
+    return RSH_OK;
+}
+
+int rsh_block_sums_batch_wire(rsh_ctx* ctx, rsh_block_wire_job* jobs, int32_t njobs, const uint8_t seed[4]) {
+    if (!ctx || !seed || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
+    std::vector<int64_t> n((size_t)njobs, 0);
+    std::vector<int32_t> run;  // files with chunks
+    for (int32_t i = 0; i < njobs; ++i) {
+        rsh_block_wire_job& j = jobs[i];
+        j.status = RSH_OK;
+        j.out_len = 0;
+        n[(size_t)i] = pieces_len(j.pieces, j.npieces);
+        if (n[(size_t)i] < 0) {
+            j.status = RSH_E_INVAL;
+            continue;
+        }
+        j.status = check_generator_header(n[(size_t)i], &j.h);
+        if (j.status != RSH_OK) continue;
+        j.out_len = rsh_sums_wire_size(&j.h);
+        if (j.out_cap < j.out_len) j.status = RSH_E_NOSPACE;
+        else if (!j.out) j.status = RSH_E_INVAL;
+        if (j.status != RSH_OK) continue;
+        if (j.h.chunk_count == 0) rsh_generator_bytes(&j.h, nullptr, nullptr, j.out, j.out_cap);  // the header alone
+        else run.push_back(i);
+    }
+    if (!run.empty()) {
+        // as rsh_block_sums_batch: a failure leaves no unfinished file at RSH_OK
+        std::vector<char> done((size_t)njobs, 0);
+        const int rc = block_wire_passes(ctx, jobs, run, n, seed, done);
+        if (rc != RSH_OK) {
+            (void)hipStreamSynchronize(ctx->stream);  // no copy from the caller's buffers outlives the call
+            for (int32_t i : run)
+                if (!done[(size_t)i] && jobs[i].status == RSH_OK) jobs[i].status = rc;
+            return rc;
+        }
+    }
+    for (int32_t i = 0; i < njobs; ++i)
+        if (jobs[i].status != RSH_OK) return jobs[i].status;
+    return RSH_OK;
+}
+
+int rsh_match_scan_batch_wire(rsh_ctx* ctx, rsh_send_job* jobs, int32_t njobs, const uint8_t seed[4],
+                              rsh_scan_stats* stats) {
+    if (!ctx || !seed || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
+    if (stats) *stats = rsh_scan_stats{};
+    std::vector<int64_t> n((size_t)njobs, 0);
+    std::vector<int32_t> ok;        // every file with a valid job (its MD5 runs)
+    std::vector<int32_t> dev, host; // ... scanned in passes / handed to the device batch without bytes
+    for (int32_t i = 0; i < njobs; ++i) {
+        rsh_send_job& j = jobs[i];
+        j.status = RSH_OK;
+        j.n_ev = j.literal = j.matched = j.out_len = 0;
+        memset(j.file_md5, 0, 16);
+        n[(size_t)i] = pieces_len(j.pieces, j.npieces);
+        if (n[(size_t)i] < 0) j.status = RSH_E_INVAL;
+        if (j.status == RSH_OK) j.status = rsh_header_validate(&j.h);
+        if (j.status == RSH_OK &&
+            (j.table_len != rsh_sums_wire_size(&j.h) - 16 || (j.table_len > 0 && !j.table)))
+            j.status = RSH_E_INVAL;
+        j.out_status = j.status;
+        if (j.status != RSH_OK) continue;
+        ok.push_back(i);
+        (j.h.block_length > 0 && n[(size_t)i] > 0 ? dev : host).push_back(i);
+    }
+    if (ok.empty()) {
+        for (int32_t i = 0; i < njobs; ++i)
+            if (jobs[i].status != RSH_OK) return jobs[i].status;
+        return RSH_OK;
+    }
+    // as rsh_match_scan_batch: a failure leaves no file it did not finish at RSH_OK
+    std::vector<char> done((size_t)njobs, 0);
+    auto fail_unfinished = [&](int code) {
+        for (int32_t i : ok)
+            if (!done[(size_t)i] && jobs[i].status == RSH_OK) jobs[i].status = jobs[i].out_status = code;
+        return code;
+    };
+    CtxClaim claim_(ctx);
+    if (!claim_.held) {
+        snprintf(g_last_err, sizeof(g_last_err), "context in use by another thread");
+        return fail_unfinished(RSH_E_BUSY);
+    }
+    if (const hipError_t e = hipSetDevice(ctx->device); e != hipSuccess) {
+        note_error(e, __LINE__, "segment.cpp");
+        return fail_unfinished(RSH_E_DEVICE);
+    }
+    constexpr int kScanCores = 3;  // (the split of rsh_match_scan_batch)
+    const int cores = rsh::call_cores();
+    const int md5_threads = std::max(1, cores - kScanCores);
+    rsh::WorkerCap cap(std::max(1, cores - md5_threads));
+    std::vector<rsh::Md5File> mf;
+    for (int32_t i : ok) mf.push_back(rsh::Md5File{jobs[i].pieces, jobs[i].npieces});
+    std::vector<uint8_t> md5((size_t)ok.size() * 16 + 16);
+    std::thread md5_thread([&] {
+        rsh::md5_files(mf.data(), (int32_t)mf.size(), reinterpret_cast<uint8_t(*)[16]>(md5.data()), md5_threads,
+                       (int)rsh::opt(rsh::OPT_MD5_WIDTH));
+    });
+    // A scanned file's result into its job; whether its stream can be written (the events are there, `out` holds it).
+    auto take = [&](rsh_send_job& j, const rsh_scan_job& x) {
+        j.status = j.out_status = x.status;
+        j.n_ev = x.n_ev;
+        j.literal = x.literal;
+        j.matched = x.matched;
+        if (j.status != RSH_OK) return false;
+        j.out_len = rsh_tokens_size(j.ev, j.n_ev);
+        if (j.out_cap < j.out_len) j.out_status = RSH_E_NOSPACE;
+        else if (!j.out) j.out_status = RSH_E_INVAL;
+        return j.out_status == RSH_OK;
+    };
+    int rc = RSH_OK;
+    // new files (skipMatchSendData) and empty sources: no bytes to copy, their streams framed from the pieces
+    if (!host.empty()) {
+        std::vector<rsh_scan_job> sj;
+        for (int32_t i : host) {
+            const rsh_send_job& j = jobs[i];
+            rsh_scan_job x{};
+            x.n = n[(size_t)i];
+            x.h = j.h;
+            x.ev = j.ev;
+            x.ev_cap = j.ev_cap;
+            sj.push_back(x);
+        }
+        rc = rsh::match_scan_batch_claimed(ctx, sj.data(), (int32_t)sj.size(), seed, nullptr);
+        for (size_t k = 0; k < sj.size(); ++k) {
+            rsh_send_job& j = jobs[host[k]];
+            const bool framed = take(j, sj[k]);
+            if (rc != RSH_OK && rc != RSH_E_NOSPACE) continue;
+            if (framed) tokens_from_pieces(j.pieces, j.npieces, j.ev, j.n_ev, j.out);
+            done[(size_t)host[k]] = 1;
+        }
+        if (rc == RSH_E_NOSPACE) rc = RSH_OK;  // per file
+    }
+    for (const Pass& pass : plan_passes(dev, n)) {
+        if (rc != RSH_OK && rc != RSH_E_NOSPACE) break;
+        if (pass.alone) {  // larger than a pass: the tiled single-file scan over the table unframed on the host
+            rsh_send_job& j = jobs[pass.files[0]];
+            const size_t C = (size_t)j.h.chunk_count, dl = (size_t)j.h.digest_length;
+            std::vector<int32_t> weak(C + 1);
+            std::vector<uint8_t> strong(C * dl + 1);
+            rsh::sums_unframe_host(j.h, j.table, weak.data(), strong.data());
+            rsh::ResolveResult r;
+            j.status = rsh::scan_pieces_claimed(ctx, j.pieces, j.npieces, n[(size_t)pass.files[0]], &j.h, weak.data(),
+                                                strong.data(), seed, &r);
+            if (j.status == RSH_OK) {
+                j.literal = r.literal;
+                j.matched = r.matched;
+                if (stats) rsh::add_scan_stats(stats, r.stats);
+                j.status = emit_events(ctx, r, j.ev, j.ev_cap, &j.n_ev);
+            }
+            // the source went through HBM a tile at a time: the caller replays the literals (rsh_tokens_write_kept's rule)
+            j.out_status = j.status == RSH_OK ? RSH_E_NOSOURCE : j.status;
+            if (j.status == RSH_OK) j.out_len = rsh_tokens_size(j.ev, j.n_ev);
+            done[(size_t)pass.files[0]] = 1;
+            if (j.status != RSH_OK && j.status != RSH_E_NOSPACE) rc = j.status;
+            continue;
+        }
+        int64_t data_bytes = 0, tab_bytes = 0;
+        for (int32_t f : pass.files) {
+            data_bytes += align_up(n[(size_t)f]);
+            tab_bytes += align_up(4 * (int64_t)jobs[f].h.chunk_count) +
+                         align_up((int64_t)jobs[f].h.chunk_count * jobs[f].h.digest_length);
+        }
+        if (fail_alloc() || ctx->seg_data.ensure((size_t)data_bytes + kAlign) != hipSuccess ||
+            ctx->seg_tab.ensure((size_t)tab_bytes + kAlign) != hipSuccess) {
+            snprintf(g_last_err, sizeof(g_last_err), "segment pass of %lld bytes: device memory (segment.cpp)",
+                     (long long)(data_bytes + tab_bytes));
+            rc = RSH_E_NOMEM;
+            break;
+        }
+        std::vector<rsh_scan_job> sj;
+        std::vector<rsh::SumsUnframeWork> uw;
+        int64_t doff = 0, toff = 0;
+        for (int32_t f : pass.files) {
+            const rsh_send_job& j = jobs[f];
+            const int64_t C = j.h.chunk_count, dl = j.h.digest_length;
+            uint8_t* w = ctx->seg_tab.as<uint8_t>() + toff;
+            rsh_scan_job x{};
+            x.d_src = ctx->seg_data.as<uint8_t>() + doff;
+            x.n = n[(size_t)f];
+            x.h = j.h;
+            x.d_weak = w;
+            x.d_strong = w + align_up(4 * C);
+            x.ev = j.ev;
+            x.ev_cap = j.ev_cap;
+            sj.push_back(x);
+            uw.push_back(rsh::SumsUnframeWork{j.h, j.table, w, w + align_up(4 * C)});
+            doff += align_up(x.n);
+            toff += align_up(4 * C) + align_up(C * dl);
+        }
+        // the tables first (megabytes, raw: one copy and one sums_unframe_kernel launch per staging piece), then the
+        // sources: the wait for the tables' staging does not wait for the files
+        const int urc = rsh::sums_unframe_files(ctx, uw.data(), uw.size());
+        if (urc != RSH_OK) {
+            rc = urc;
+            break;
+        }
+        hipError_t e = hipSuccess;
+        for (size_t k = 0; k < sj.size() && e == hipSuccess; ++k) {
+            const rsh_send_job& j = jobs[pass.files[k]];
+            e = fail_copy(copy_pieces(j.pieces, j.npieces, (uint8_t*)sj[k].d_src, ctx->stream));
+        }
+        if (e != hipSuccess) {
+            note_error(e, __LINE__, "segment.cpp");
+            rc = RSH_E_DEVICE;
+            break;
+        }
+        rsh_scan_stats ps{};
+        const int prc = rsh::match_scan_batch_claimed(ctx, sj.data(), (int32_t)sj.size(), seed, stats ? &ps : nullptr);
+        if (stats) rsh::add_scan_stats(stats, ps);
+        // the pass's replies, framed while its sources are in seg_data (before the next pass's copies are queued)
+        std::vector<rsh_token_job> tj;
+        std::vector<int32_t> owner;
+        for (size_t k = 0; k < sj.size(); ++k) {
+            rsh_send_job& j = jobs[pass.files[k]];
+            const bool framed = take(j, sj[k]);
+            if (prc != RSH_OK && prc != RSH_E_NOSPACE) continue;
+            if (framed) {
+                rsh_token_job t{};
+                t.d_src = sj[k].d_src;
+                t.n = sj[k].n;
+                t.ev = j.ev;
+                t.n_ev = j.n_ev;
+                t.out = j.out;
+                t.out_cap = j.out_cap;
+                tj.push_back(t);
+                owner.push_back(pass.files[k]);
+            } else {
+                done[(size_t)pass.files[k]] = 1;
+            }
+        }
+        if (prc != RSH_OK && prc != RSH_E_NOSPACE) {
+            rc = prc;
+            break;
+        }
+        const int trc = tj.empty() ? RSH_OK : rsh::tokens_write_batch_claimed(ctx, tj.data(), (int32_t)tj.size());
+        for (size_t k = 0; k < tj.size(); ++k) {
+            jobs[owner[k]].out_status = tj[k].status;
+            if (trc == RSH_OK || tj[k].status == RSH_OK) done[(size_t)owner[k]] = 1;
+        }
+        if (trc == RSH_E_DEVICE) rc = trc;
+    }
+    md5_thread.join();
+    if (rc != RSH_OK) (void)hipStreamSynchronize(ctx->stream);  // no copy from the caller's buffers outlives the call
+    for (size_t k = 0; k < ok.size(); ++k) {
+        rsh_send_job& j = jobs[ok[k]];
+        memcpy(j.file_md5, md5.data() + 16 * k, 16);
+        if (j.out_status == RSH_OK && j.status == RSH_OK && j.out_len >= 20) {  // putInt(0) (:1316) and the MD5 (:1148)
+            memset(j.out + j.out_len - 20, 0, 4);
+            memcpy(j.out + j.out_len - 16, j.file_md5, 16);
+        }
+    }
     if (rc != RSH_OK) return fail_unfinished(rc);
     for (int32_t i = 0; i < njobs; ++i)
         if (jobs[i].status != RSH_OK) return jobs[i].status;

@@ -226,6 +226,12 @@ int rsh_tokens_write_batch_device(rsh_ctx* ctx, rsh_token_job* jobs, int32_t njo
     if (!ctx || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
     RSH_CLAIM_KEEP(ctx);
     RSH_HIP(hipSetDevice(ctx->device));
+    return tokens_write_batch_claimed(ctx, jobs, njobs);
+}
+
+}  // extern "C"
+
+int rsh::tokens_write_batch_claimed(rsh_ctx* ctx, rsh_token_job* jobs, int32_t njobs) {
     std::vector<TokWork> works;
     std::vector<int32_t> owner;
     works.reserve((size_t)njobs);
@@ -263,6 +269,8 @@ int rsh_tokens_write_batch_device(rsh_ctx* ctx, rsh_token_job* jobs, int32_t njo
         if (jobs[f].status != RSH_OK) return jobs[f].status;
     return RSH_OK;
 }
+
+extern "C" {
 
 int rsh_debug_tokens_selftest(const uint8_t* src, int64_t n, const rsh_event* ev, int64_t n_ev,
                               const uint8_t file_md5[16], int64_t from, uint8_t* out, int64_t len, int64_t span,

@@ -313,6 +313,78 @@ final class NativeChecksum implements AutoCloseable {
         return events;
     }
 
+    /** Reply flags of matchScanSegmentWire (RSH_E_NOSPACE / RSH_E_NOSOURCE): the caller replays that file's events. */
+    static final int REPLY_OK = 0, REPLY_NOSPACE = -4, REPLY_NOSOURCE = -10;
+
+    /** The bytes of a file's header + table on the Generator's channel (rsh_sums_wire_size). */
+    static long sumsWireSize(Checksum.Header h) {
+        return 16 + (long) h.getChunkCount() * (4 + h.getDigestLength());
+    }
+
+    /**
+     * A segment's Generator pass in channel bytes (Generator.itemizeSegment): wire[f] (a direct buffer of at least
+     * sumsWireSize(headers[f]) bytes) receives file f's header + table exactly as sendItemizeAndChecksums writes
+     * them; its limit is set to their size, so the hook is {@code out.put(wire[f])}.
+     */
+    void blockSumsSegmentWire(ByteBuffer[][] basis, long[] sizes, Checksum.Header[] headers, byte[] seed,
+            ByteBuffer[] wire) {
+        Segment s = new Segment(basis, headers);
+        long[] len = new long[headers.length];
+        lock.lock();
+        try {
+            blockSumsSegmentWire(handles(), s.buffers, s.filePieces, sizes, s.headers, seed, wire, len);
+        } finally {
+            lock.unlock();
+        }
+        for (int f = 0; f < wire.length; f++) {
+            wire[f].position(0).limit((int) len[f]);
+        }
+    }
+
+    /**
+     * A segment's Sender pass in channel bytes (Sender.sendFiles): tables[f] holds file f's records as
+     * {@code duplexChannel.get(tables[f])} read them (position 0 to its limit), replies[f] receives the file's whole
+     * reply (tokens, putInt(0), MD5).  Returns the events per file as matchScanSegment does; flags[f] is REPLY_OK
+     * (replies[f] is ready: position 0, limit the reply's size), or REPLY_NOSPACE / REPLY_NOSOURCE: the caller then
+     * replays events[f] as after matchScanSegment.  replySizes[f] is the reply's size either way.
+     */
+    long[][] matchScanSegmentWire(ByteBuffer[][] source, long[] fileSizes, Checksum.Header[] headers,
+            ByteBuffer[] tables, byte[] seed, ByteBuffer[] replies, byte[][] fileMd5, long[][] sizes, int[] flags,
+            long[] replySizes) {
+        Segment s = new Segment(source, headers);
+        int nf = headers.length;
+        byte[] md5 = new byte[16 * nf];
+        long[] per = new long[5 * nf];
+        long[] tableLens = new long[nf];
+        for (int f = 0; f < nf; f++) {
+            tableLens[f] = tables[f] == null ? 0 : tables[f].limit();
+        }
+        long[] flat;
+        lock.lock();
+        try {
+            flat = matchScanSegmentWire(handles(), s.buffers, s.filePieces, fileSizes, s.headers, tables, tableLens,
+                    seed, replies, md5, per);
+        } finally {
+            lock.unlock();
+        }
+        long[][] events = new long[nf][];
+        int at = 0;
+        for (int f = 0; f < nf; f++) {
+            int len = (int) (4 * per[5 * f]);
+            events[f] = java.util.Arrays.copyOfRange(flat, at, at + len);
+            at += len;
+            System.arraycopy(md5, 16 * f, fileMd5[f], 0, 16);
+            sizes[f][0] = per[5 * f + 1];
+            sizes[f][1] = per[5 * f + 2];
+            replySizes[f] = per[5 * f + 3];
+            flags[f] = (int) per[5 * f + 4];
+            if (flags[f] == REPLY_OK) {
+                replies[f].position(0).limit((int) replySizes[f]);
+            }
+        }
+        return events;
+    }
+
     /** One file's precomputed table (the Generator's segment hook, INTEGRATION.md). */
     static final class Sums {
         final Checksum.Header header;
@@ -412,6 +484,13 @@ final class NativeChecksum implements AutoCloseable {
 
     static native long[] matchScanBatchMulti(long[] ctxs, ByteBuffer[] src, int[] filePieces, long[] sizes,
             int[] headers, int[][] weak, byte[][] strong, byte[] seed, byte[] fileMd5Out, long[] perFileOut);
+
+    static native void blockSumsSegmentWire(long[] ctxs, ByteBuffer[] data, int[] filePieces, long[] sizes,
+            int[] headers, byte[] seed, ByteBuffer[] wire, long[] wireLenOut);
+
+    static native long[] matchScanSegmentWire(long[] ctxs, ByteBuffer[] src, int[] filePieces, long[] sizes,
+            int[] headers, ByteBuffer[] tables, long[] tableLens, byte[] seed, ByteBuffer[] replies,
+            byte[] fileMd5Out, long[] perFileOut);
 
     static native boolean receiverCombine(long ctx, ByteBuffer tokens, long tokensLen, int[] header,
             ByteBuffer replica, long replicaLen, boolean deferWrite, ByteBuffer target, long targetCap,

@@ -26,7 +26,10 @@
  *   blockSumsBatch / matchScanBatch    a whole file-list segment in one call (Generator.itemizeSegment,
  *                                      Sender.sendFiles): every file's pieces, header and table at once;
  *   blockSumsBatchMulti / matchScanBatchMulti  the same over the calling thread's contexts on the node's GPUs
- *                                      (rsh_*_batch_multi: the segment's files split over them).
+ *                                      (rsh_*_batch_multi: the segment's files split over them);
+ *   blockSumsSegmentWire / matchScanSegmentWire  the segment in channel bytes: each file's header + table, its
+ *                                      received records and its whole reply in direct ByteBuffers
+ *                                      (rsh_*_batch_wire_multi), so that Java moves each with one bulk put / get.
  * The Sender replays the returned events through its own sendDataFrom/putInt so channel framing is
  * untouched (Sender.java:794-809); INTEGRATION.md shows the replay for each form.  tokensKept is that replay done
  * by the library from the source the scan left in HBM (the path form's first choice).
@@ -835,6 +838,215 @@ JNIEXPORT jlongArray JNICALL Java_com_github_java_rsync_internal_session_NativeC
     rsh_ctx** cs = ctxs_of(env, ctxs, &n);
     if (!cs) return NULL;
     jlongArray out = scan_segment(env, cs, n, src, filePieces, sizes, hdrs, weak, strong, seed, fileMd5Out, perFileOut);
+    free(cs);
+    return out;
+}
+
+/* ---- a segment in channel bytes (rsh_block_sums_batch_wire_multi / rsh_match_scan_batch_wire_multi) ----
+ * The tables and the replies travel in direct ByteBuffers, one per file, so that the Java side moves each with one bulk
+ * put / get.  Every length is checked against its buffer's capacity before the library sees the address. */
+
+/* The direct buffers of bufs[0 .. nf): addr[f] / cap[f] (a null element: NULL / 0 when allowed).  RSH_OK, or
+ * IllegalArgumentException thrown. */
+static int direct_array(JNIEnv* env, jobjectArray bufs, jint nf, int null_ok, uint8_t** addr, jlong* cap) {
+    if (!bufs || (*env)->GetArrayLength(env, bufs) < nf) {
+        throw_status(env, RSH_E_INVAL);
+        return RSH_E_INVAL;
+    }
+    for (jint f = 0; f < nf; ++f) {
+        jobject b = (*env)->GetObjectArrayElement(env, bufs, f);
+        addr[f] = b ? (uint8_t*)(*env)->GetDirectBufferAddress(env, b) : NULL;
+        cap[f] = b ? (*env)->GetDirectBufferCapacity(env, b) : 0;
+        const int bad = b ? (!addr[f] || cap[f] < 0) : !null_ok;
+        if (b) (*env)->DeleteLocalRef(env, b);
+        if (bad) {
+            throw_class(env, "java/lang/IllegalArgumentException", "not a direct ByteBuffer");
+            return RSH_E_INVAL;
+        }
+    }
+    return RSH_OK;
+}
+
+/* wire[f] receives file f's header + table exactly as Generator.sendItemizeAndChecksums writes them;
+ * wireLenOut[f] = their size.  A wire[f] smaller than that is an IllegalArgumentException (nothing runs). */
+JNIEXPORT void JNICALL Java_com_github_java_rsync_internal_session_NativeChecksum_blockSumsSegmentWire(
+    JNIEnv* env, jclass cls, jlongArray ctxs, jobjectArray data, jintArray filePieces, jlongArray sizes, jintArray hdrs,
+    jbyteArray seed, jobjectArray wire, jlongArray wireLenOut) {
+    (void)cls;
+    jint nctx = 0;
+    rsh_ctx** cs = ctxs_of(env, ctxs, &nctx);
+    if (!cs) return;
+    jbyte s4[4];
+    segment_args a;
+    if (seed_from(env, seed, s4) != RSH_OK) {
+        throw_status(env, RSH_E_INVAL);
+        free(cs);
+        return;
+    }
+    if (segment_from(env, data, filePieces, sizes, hdrs, &a) != RSH_OK) {
+        free(cs);
+        return;
+    }
+    const jint nf = a.nf;
+    rsh_block_wire_job* jobs = (rsh_block_wire_job*)calloc((size_t)nf + 1, sizeof(rsh_block_wire_job));
+    uint8_t** addr = (uint8_t**)calloc((size_t)nf + 1, sizeof(uint8_t*));
+    jlong* cap = (jlong*)calloc((size_t)nf + 1, sizeof(jlong));
+    int rc = (jobs && addr && cap) ? RSH_OK : RSH_E_NOMEM;
+    if (rc != RSH_OK) throw_status(env, rc);
+    if (rc == RSH_OK && (!wireLenOut || (*env)->GetArrayLength(env, wireLenOut) < nf)) throw_status(env, rc = RSH_E_INVAL);
+    if (rc == RSH_OK) rc = direct_array(env, wire, nf, 0, addr, cap);
+    for (jint f = 0; rc == RSH_OK && f < nf; ++f) {
+        jobs[f].pieces = a.pieces + a.first[f];
+        jobs[f].npieces = a.count[f];
+        jobs[f].h = a.h[f];
+        jobs[f].out = addr[f];
+        jobs[f].out_cap = cap[f];
+        const int64_t need = rsh_sums_wire_size(&a.h[f]);
+        if (need < 0 || cap[f] < need) {
+            rc = RSH_E_INVAL;
+            throw_class(env, "java/lang/IllegalArgumentException",
+                        need < 0 ? "bad checksum header" : "header and table exceed the direct buffer's capacity");
+        }
+    }
+    if (rc == RSH_OK) {
+        rc = rsh_block_sums_batch_wire_multi(cs, nctx, jobs, nf, (const uint8_t*)s4);
+        if (rc != RSH_OK) {
+            jint f = 0;
+            while (f < nf && jobs[f].status == RSH_OK) ++f;
+            if (f < nf) throw_file_status(env, f, jobs[f].status);
+            else throw_status(env, rc); /* the call failed before any file did */
+        } else {
+            for (jint f = 0; f < nf; ++f) {
+                const jlong len = jobs[f].out_len;
+                (*env)->SetLongArrayRegion(env, wireLenOut, f, 1, &len);
+            }
+        }
+    }
+    free(jobs);
+    free(addr);
+    free(cap);
+    segment_free(&a);
+    free(cs);
+}
+
+/* tables[f]: file f's records as they came off the channel, tableLens[f] bytes (tables[f] may be null when that is 0);
+ * replies[f]: receives file f's channel bytes (tokens, putInt(0), MD5), its capacity the room offered.  Returns the
+ * events as matchScanBatch does; perFileOut[5f .. 5f+4] = {event count, sizeLiteral, sizeMatch, reply size, reply
+ * flag}, the flag 0 when replies[f] holds the reply, RSH_E_NOSPACE (-4) when its capacity is short of the reply size,
+ * RSH_E_NOSOURCE (-10) for a file larger than a pass (scanned tiled): flags, not exceptions -- the caller replays such
+ * a file's events itself.  A caller that must flip md5[0] after a read error (Sender.java:1136-1143) overwrites the
+ * last 16 bytes of replies[f]. */
+JNIEXPORT jlongArray JNICALL Java_com_github_java_rsync_internal_session_NativeChecksum_matchScanSegmentWire(
+    JNIEnv* env, jclass cls, jlongArray ctxs, jobjectArray src, jintArray filePieces, jlongArray sizes, jintArray hdrs,
+    jobjectArray tables, jlongArray tableLens, jbyteArray seed, jobjectArray replies, jbyteArray fileMd5Out,
+    jlongArray perFileOut) {
+    (void)cls;
+    jint nctx = 0;
+    rsh_ctx** cs = ctxs_of(env, ctxs, &nctx);
+    if (!cs) return NULL;
+    jbyte s4[4];
+    segment_args a;
+    if (seed_from(env, seed, s4) != RSH_OK) {
+        throw_status(env, RSH_E_INVAL);
+        free(cs);
+        return NULL;
+    }
+    if (segment_from(env, src, filePieces, sizes, hdrs, &a) != RSH_OK) {
+        free(cs);
+        return NULL;
+    }
+    const jint nf = a.nf;
+    rsh_send_job* jobs = (rsh_send_job*)calloc((size_t)nf + 1, sizeof(rsh_send_job));
+    uint8_t** taddr = (uint8_t**)calloc((size_t)nf + 1, sizeof(uint8_t*));
+    uint8_t** raddr = (uint8_t**)calloc((size_t)nf + 1, sizeof(uint8_t*));
+    jlong* tcap = (jlong*)calloc((size_t)nf + 1, sizeof(jlong));
+    jlong* rcap = (jlong*)calloc((size_t)nf + 1, sizeof(jlong));
+    jlong* tlen = (jlong*)calloc((size_t)nf + 1, sizeof(jlong));
+    int rc = (jobs && taddr && raddr && tcap && rcap && tlen) ? RSH_OK : RSH_E_NOMEM;
+    if (rc != RSH_OK) throw_status(env, rc);
+    if (rc == RSH_OK && (!tableLens || !fileMd5Out || !perFileOut || (*env)->GetArrayLength(env, tableLens) < nf ||
+                         (*env)->GetArrayLength(env, fileMd5Out) < 16 * (jlong)nf ||
+                         (*env)->GetArrayLength(env, perFileOut) < 5 * (jlong)nf))
+        throw_status(env, rc = RSH_E_INVAL);
+    if (rc == RSH_OK) rc = direct_array(env, tables, nf, 1, taddr, tcap);
+    if (rc == RSH_OK) rc = direct_array(env, replies, nf, 0, raddr, rcap);
+    if (rc == RSH_OK && nf > 0) (*env)->GetLongArrayRegion(env, tableLens, 0, nf, tlen);
+    for (jint f = 0; rc == RSH_OK && f < nf; ++f) {
+        if (tlen[f] < 0 || tlen[f] > tcap[f]) {
+            rc = RSH_E_INVAL;
+            throw_class(env, "java/lang/IllegalArgumentException", "table length exceeds the direct buffer's capacity");
+            break;
+        }
+        int64_t n = 0;
+        for (int32_t k = 0; k < a.count[f]; ++k) n += a.pieces[a.first[f] + k].len;
+        jobs[f].pieces = a.pieces + a.first[f];
+        jobs[f].npieces = a.count[f];
+        jobs[f].h = a.h[f];
+        jobs[f].table = taddr[f];
+        jobs[f].table_len = tlen[f];
+        jobs[f].ev_cap = event_bound(n, &a.h[f]);
+        jobs[f].ev = (rsh_event*)malloc((size_t)jobs[f].ev_cap * sizeof(rsh_event));
+        jobs[f].out = raddr[f];
+        jobs[f].out_cap = rcap[f];
+        if (!jobs[f].ev) throw_status(env, rc = RSH_E_NOMEM);
+    }
+    jlongArray out = NULL;
+    if (rc == RSH_OK) {
+        rc = rsh_match_scan_batch_wire_multi(cs, nctx, jobs, nf, (const uint8_t*)s4, NULL);
+        /* (event_bound cannot be outrun, see above; should it ever be, the file is scanned again alone) */
+        for (jint f = 0; rc == RSH_E_NOSPACE && f < nf; ++f) {
+            if (jobs[f].status != RSH_E_NOSPACE) continue;
+            rsh_event* ev = (rsh_event*)realloc(jobs[f].ev, ((size_t)jobs[f].n_ev + 1) * sizeof(rsh_event));
+            if (!ev) {
+                rc = RSH_E_NOMEM;
+                break;
+            }
+            jobs[f].ev = ev;
+            jobs[f].ev_cap = jobs[f].n_ev;
+            const int r1 = rsh_match_scan_batch_wire(cs[0], &jobs[f], 1, (const uint8_t*)s4, NULL);
+            if (r1 != RSH_OK) rc = r1;
+        }
+        if (rc == RSH_E_NOSPACE) rc = RSH_OK;
+        jint bad = 0;
+        while (bad < nf && jobs[bad].status == RSH_OK) ++bad;
+        if (bad < nf) {
+            throw_file_status(env, bad, jobs[bad].status);
+        } else if (rc != RSH_OK) {
+            throw_status(env, rc); /* the call failed before any file did */
+        } else {
+            int64_t total = 0;
+            for (jint f = 0; f < nf; ++f) total += jobs[f].n_ev;
+            out = (*env)->NewLongArray(env, (jsize)(4 * total));
+            jlong* o = out ? (*env)->GetLongArrayElements(env, out, NULL) : NULL;
+            if (o) {
+                int64_t q = 0;
+                for (jint f = 0; f < nf; ++f) {
+                    const rsh_event* ev = jobs[f].ev;
+                    for (int64_t i = 0; i < jobs[f].n_ev; ++i, ++q) {
+                        o[4 * q + 0] = ev[i].kind;
+                        o[4 * q + 1] = ev[i].offset;
+                        o[4 * q + 2] = ev[i].length;
+                        o[4 * q + 3] = (jlong)(uint32_t)ev[i].index | ((jlong)ev[i].count << 32);
+                    }
+                    const jlong per[5] = {jobs[f].n_ev, jobs[f].literal, jobs[f].matched, jobs[f].out_len,
+                                          jobs[f].out_status};
+                    (*env)->SetLongArrayRegion(env, perFileOut, 5 * f, 5, per);
+                    (*env)->SetByteArrayRegion(env, fileMd5Out, 16 * f, 16, (const jbyte*)jobs[f].file_md5);
+                }
+                (*env)->ReleaseLongArrayElements(env, out, o, 0);
+            } else {
+                out = NULL; /* OutOfMemoryError pending */
+            }
+        }
+    }
+    for (jint f = 0; jobs && f < nf; ++f) free(jobs[f].ev);
+    free(jobs);
+    free(taddr);
+    free(raddr);
+    free(tcap);
+    free(rcap);
+    free(tlen);
+    segment_free(&a);
     free(cs);
     return out;
 }

@@ -131,6 +131,22 @@ class ScanBatchJob(ctypes.Structure):
                 ("matched", ctypes.c_int64), ("file_md5", ctypes.c_uint8 * 16)]
 
 
+class BlockWireJob(ctypes.Structure):
+    """rsh_block_wire_job: one basis file of a segment's Generator pass, its table in wire form."""
+    _fields_ = [("pieces", ctypes.POINTER(Piece)), ("npieces", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("h", Header), ("out", ctypes.c_void_p), ("out_cap", ctypes.c_int64), ("out_len", ctypes.c_int64)]
+
+
+class SendJob(ctypes.Structure):
+    """rsh_send_job: one transfer request of a segment's Sender pass (records in, events and channel bytes out)."""
+    _fields_ = [("pieces", ctypes.POINTER(Piece)), ("npieces", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("h", Header), ("table", ctypes.c_void_p), ("table_len", ctypes.c_int64), ("ev", ctypes.c_void_p),
+                ("ev_cap", ctypes.c_int64), ("n_ev", ctypes.c_int64), ("literal", ctypes.c_int64),
+                ("matched", ctypes.c_int64), ("file_md5", ctypes.c_uint8 * 16), ("out", ctypes.c_void_p),
+                ("out_cap", ctypes.c_int64), ("out_len", ctypes.c_int64), ("out_status", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class TokenJob(ctypes.Structure):
     """rsh_token_job: one file of rsh_tokens_write_batch_device (device source, host events and output)."""
     _fields_ = [("d_src", ctypes.c_void_p), ("n", ctypes.c_int64), ("ev", ctypes.c_void_p), ("n_ev", ctypes.c_int64),
@@ -154,11 +170,14 @@ EXPORTS = ["rsh_abi_version", "rsh_strerror", "rsh_last_error", "rsh_device_coun
            "rsh_match_scan_device", "rsh_match_scan_tiled", "rsh_fetch_events", "rsh_file_md5", "rsh_tokens_size", "rsh_tokens_write", "rsh_generator_bytes",
            "rsh_block_sums_batch_device", "rsh_match_scan_batch_device", "rsh_receiver_combine",
            "rsh_receiver_combine_device", "rsh_receiver_combine_batch", "rsh_block_sums_file", "rsh_match_scan_file", "rsh_block_sums_pieces", "rsh_match_scan_pieces", "rsh_block_sums_batch", "rsh_match_scan_batch", "rsh_block_sums_batch_multi", "rsh_match_scan_batch_multi", "rsh_receiver_combine_batch_multi", "rsh_shard_files", "rsh_file_md5_batch", "rsh_dev_alloc", "rsh_dev_free", "rsh_memcpy_h2d", "rsh_memcpy_d2h", "rsh_fill_splitmix_device",
-           "rsh_tokens_write_device", "rsh_tokens_write_kept", "rsh_tokens_write_batch_device"]
+           "rsh_tokens_write_device", "rsh_tokens_write_kept", "rsh_tokens_write_batch_device",
+           "rsh_sums_wire_size", "rsh_header_from_wire", "rsh_sums_frame_device", "rsh_sums_unframe_device",
+           "rsh_block_sums_batch_wire", "rsh_match_scan_batch_wire", "rsh_block_sums_batch_wire_multi",
+           "rsh_match_scan_batch_wire_multi"]
 # include/rsync_hip_debug.h (testing / diagnostics ABI)
 DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_reset_options", "rsh_debug_k1_clock",
                  "rsh_debug_streams_busy", "rsh_debug_kernel_ms", "rsh_debug_multi_selftest", "rsh_debug_generation",
-                 "rsh_debug_tokens_selftest"]
+                 "rsh_debug_tokens_selftest", "rsh_debug_sums_selftest"]
 
 _LIB = None
 
@@ -264,6 +283,17 @@ def lib():
         "rsh_tokens_write_kept": ([P, P, I64, P, I64, P, I64], ctypes.c_int),
         "rsh_tokens_write_batch_device": ([P, ctypes.POINTER(TokenJob), I32], ctypes.c_int),
         "rsh_debug_tokens_selftest": ([P, I64, P, I64, P, I64, P, I64, I64, ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_sums_wire_size": ([HP], I64),
+        "rsh_header_from_wire": ([P, HP], ctypes.c_int),
+        "rsh_sums_frame_device": ([P, HP, P, P, P, I64], ctypes.c_int),
+        "rsh_sums_unframe_device": ([P, HP, P, I64, P, P], ctypes.c_int),
+        "rsh_block_sums_batch_wire": ([P, ctypes.POINTER(BlockWireJob), I32, P], ctypes.c_int),
+        "rsh_match_scan_batch_wire": ([P, ctypes.POINTER(SendJob), I32, P, ctypes.POINTER(ScanStats)], ctypes.c_int),
+        "rsh_block_sums_batch_wire_multi": ([ctypes.POINTER(P), I32, ctypes.POINTER(BlockWireJob), I32, P],
+                                            ctypes.c_int),
+        "rsh_match_scan_batch_wire_multi": ([ctypes.POINTER(P), I32, ctypes.POINTER(SendJob), I32, P,
+                                             ctypes.POINTER(ScanStats)], ctypes.c_int),
+        "rsh_debug_sums_selftest": ([I32, HP, P, P, P, I64, I64, ctypes.POINTER(I64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -410,6 +440,35 @@ def tokens_selftest(src, ev, file_md5_bytes, start=0, length=None, span=0, out=N
     return out[:max(length, 0)].tobytes(), nd.value
 
 
+def sums_wire_size(h):
+    """rsh_sums_wire_size: the bytes of a file's header + table on the Generator's channel."""
+    return lib().rsh_sums_wire_size(ctypes.byref(h))
+
+
+def header_from_wire(wire):
+    """rsh_header_from_wire (Connection.receiveChecksumHeader): the Header of 16 received bytes; ProtocolError as
+    header_validate."""
+    a = _u8(wire)
+    if a.size != 16:
+        raise ValueError("a checksum header is 16 bytes")
+    h = Header()
+    _check(lib().rsh_header_from_wire(_ptr(a), ctypes.byref(h)))
+    return h
+
+
+def sums_selftest(h, weak=None, strong=None, wire=None, span=0, unframe=False):
+    """rsh_debug_sums_selftest: the wire-form table's planner and a host stand-in of its kernels.  Frame: weak, strong
+    (arrays) -> `wire` (a uint8 array of sums_wire_size(h) bytes, any alignment: written in place).  Unframe: `wire`
+    (the records, any alignment) -> weak (int32 array), strong (uint8 array), written in place.  Returns the
+    descriptor count."""
+    nd = ctypes.c_int64()
+    _check(lib().rsh_debug_sums_selftest(int(bool(unframe)), ctypes.byref(h), _ptr(weak) if weak is not None and weak.size else None,
+                                         _ptr(strong) if strong is not None and strong.size else None,
+                                         _ptr(wire) if wire is not None and wire.size else None,
+                                         0 if wire is None else wire.size, span, ctypes.byref(nd)))
+    return nd.value
+
+
 def set_option(name, value):
     """A library tunable or diagnostic switch (include/rsync_hip_debug.h; tests and A/B runs only)."""
     _check(lib().rsh_debug_set_option(name.encode(), int(value)))
@@ -504,6 +563,12 @@ class Context:
 
     def _combine_batch(self, jobs, n):
         return lib().rsh_receiver_combine_batch(self._p, jobs, n)
+
+    def _block_batch_wire(self, jobs, n, seed):
+        return lib().rsh_block_sums_batch_wire(self._p, jobs, n, seed)
+
+    def _scan_batch_wire(self, jobs, n, seed, stats):
+        return lib().rsh_match_scan_batch_wire(self._p, jobs, n, seed, stats)
 
     def trim(self):
         """Release the pass-sized buffers (rsh_ctx_trim); the next call allocates what it needs again."""
@@ -749,6 +814,103 @@ class Context:
             res.append((tj[i].status, out[:tj[i].out_len].tobytes() if ok else None, tj[i].out_len))
         return rc, res
 
+    def sums_frame_device(self, h, d_weak, d_strong, phase=0, cap=None, statuses=None):
+        """rsh_sums_frame_device: header + table of the sums in HBM (DeviceBuffers or device addresses) as the
+        Generator's channel bytes.  The host buffer starts `phase` bytes past a 64-byte boundary and has guard bytes on
+        both sides, which are checked after the call.  cap: the capacity to offer instead of the stream's size.
+        statuses (a list): receives the call's code instead of raising (None is returned unless it is RSH_OK)."""
+        size = sums_wire_size(h)
+        cap = size if cap is None else cap
+        whole = np.full(max(cap, 0) + 192, 0xA5, np.uint8)
+        a0 = (-whole.ctypes.data) % 64 + 64 + phase
+        out = whole[a0:a0 + max(cap, 0)]
+        ptr = [d.ptr if isinstance(d, DeviceBuffer) else ctypes.c_void_p(d or None) for d in (d_weak, d_strong)]
+        rc = lib().rsh_sums_frame_device(self._p, ctypes.byref(h), ptr[0], ptr[1], _ptr(out), cap)
+        if not ((whole[:a0] == 0xA5).all() and (whole[a0 + max(cap, 0):] == 0xA5).all()):
+            raise AssertionError("table bytes were written outside the output buffer")
+        if statuses is not None:
+            statuses[:] = [rc]
+            return out[:size].tobytes() if rc == RSH_OK else None
+        _check(rc)
+        return out[:size].tobytes()
+
+    def sums_unframe_device(self, h, records, d_weak, d_strong, length=None):
+        """rsh_sums_unframe_device: the received records (a uint8 array, any alignment) into the two arrays in HBM
+        (DeviceBuffers or device addresses)."""
+        a = records if isinstance(records, np.ndarray) else _u8(records)
+        ptr = [d.ptr if isinstance(d, DeviceBuffer) else ctypes.c_void_p(d or None) for d in (d_weak, d_strong)]
+        _check(lib().rsh_sums_unframe_device(self._p, ctypes.byref(h), _ptr(a) if a.size else None,
+                                             a.size if length is None else length, ptr[0], ptr[1]))
+
+    def block_sums_batch_wire(self, files, seed, out_caps=None, statuses=None):
+        """A segment's Generator pass with the tables in wire form (rsh_block_sums_batch_wire):
+        files = [(pieces, Header)] -> [(status, header + table bytes or None, out_len)].  out_caps: the capacity to
+        offer per file instead of its size.  statuses (a list): receives the call's code instead of raising."""
+        s = np.frombuffer(bytes(seed), np.uint8).copy()
+        jobs = (BlockWireJob * max(len(files), 1))()
+        keep = []
+        for i, (pieces, h) in enumerate(files):
+            arrs, pl, _ = _piece_list(pieces)
+            cap = out_caps[i] if out_caps is not None and out_caps[i] is not None else max(sums_wire_size(h), 0)
+            whole, out = self._guarded(cap)
+            keep.append((arrs, pl, whole, out))
+            jobs[i].pieces, jobs[i].npieces, jobs[i].h = ctypes.cast(pl, ctypes.POINTER(Piece)), len(arrs), h
+            jobs[i].out, jobs[i].out_cap = out.ctypes.data, cap
+        rc = self._block_batch_wire(jobs, len(files), _ptr(s))
+        if statuses is not None:
+            statuses[:] = [rc]
+        elif rc != RSH_E_NOSPACE:
+            _check(rc)
+        res = []
+        for i, (_, _, whole, out) in enumerate(keep):
+            if not self._guards_intact(whole):
+                raise AssertionError(f"file {i}: table bytes were written outside the output buffer")
+            ok = jobs[i].status == RSH_OK
+            res.append((jobs[i].status, out[:jobs[i].out_len].tobytes() if ok else None, jobs[i].out_len))
+        return res
+
+    def match_scan_batch_wire(self, files, seed, ev_caps=None, out_caps=None, table_lens=None, statuses=None):
+        """A segment's Sender pass in channel bytes (rsh_match_scan_batch_wire): files = [(pieces, Header, records)]
+        -> ([(events, file_md5, literal, matched, status, out_status, stream bytes or None, out_len)], stats).
+        ev_caps / out_caps / table_lens: per file, the value to offer instead of the fitting one (None: fitting).
+        statuses (a list): receives the call's code instead of raising."""
+        s = np.frombuffer(bytes(seed), np.uint8).copy()
+        jobs = (SendJob * max(len(files), 1))()
+        keep = []
+
+        def pick(lst, i, default):
+            return default if lst is None or lst[i] is None else lst[i]
+
+        for i, (pieces, h, records) in enumerate(files):
+            arrs, pl, n = _piece_list(pieces)
+            t = records if isinstance(records, np.ndarray) else _u8(records)
+            cap = pick(ev_caps, i, scan_event_cap(n, h))
+            ev = np.zeros(max(cap, 1), EVENT_DTYPE)
+            # every literal byte plus a header per 8 KiB token and per event, a match integer per chunk, the trailer
+            ocap = pick(out_caps, i, n + 4 * (n // 8192 + 1) + 4 * max(cap, 1) + 4 * max(h.chunk_count, 0) + 20)
+            whole, out = self._guarded(ocap)
+            keep.append((arrs, pl, t, ev, whole, out))
+            j = jobs[i]
+            j.pieces, j.npieces, j.h = ctypes.cast(pl, ctypes.POINTER(Piece)), len(arrs), h
+            j.table, j.table_len = (t.ctypes.data if t.size else None), pick(table_lens, i, t.size)
+            j.ev, j.ev_cap = ev.ctypes.data, cap
+            j.out, j.out_cap = out.ctypes.data, ocap
+        stats = ScanStats()
+        rc = self._scan_batch_wire(jobs, len(files), _ptr(s), ctypes.byref(stats))
+        if statuses is not None:
+            statuses[:] = [rc]
+        elif rc not in (RSH_E_NOSPACE, RSH_E_INVAL, RSH_E_PROTOCOL):
+            _check(rc)
+        res = []
+        for i, (_, _, _, ev, whole, out) in enumerate(keep):
+            if not self._guards_intact(whole):
+                raise AssertionError(f"file {i}: channel bytes were written outside the output buffer")
+            j = jobs[i]
+            evs = ev[:j.n_ev] if j.status == RSH_OK else ev[:0]
+            stream = out[:j.out_len].tobytes() if j.status == RSH_OK and j.out_status == RSH_OK else None
+            res.append((evs, bytes(j.file_md5), j.literal, j.matched, j.status, j.out_status, stream, j.out_len))
+        return res, stats.as_dict()
+
     def receiver_combine_batch(self, files, statuses=None):
         """A segment's Receiver from host memory (rsh_receiver_combine_batch; Receiver.receiveFiles):
         files = [(tokens, Header, replica pieces or None, defer_write, target_cap or None)] ->
@@ -823,6 +985,12 @@ class DeviceSet(Context):
 
     def _combine_batch(self, jobs, n):
         return lib().rsh_receiver_combine_batch_multi(self._arr, len(self.members), jobs, n)
+
+    def _block_batch_wire(self, jobs, n, seed):
+        return lib().rsh_block_sums_batch_wire_multi(self._arr, len(self.members), jobs, n, seed)
+
+    def _scan_batch_wire(self, jobs, n, seed, stats):
+        return lib().rsh_match_scan_batch_wire_multi(self._arr, len(self.members), jobs, n, seed, stats)
 
 
 def shard_files(sizes, parts):
