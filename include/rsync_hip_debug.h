@@ -8,6 +8,11 @@
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
  * fault_inject, tokens_span, tokens_piece, sums_piece.
+ *
+ * fault_inject is a bit set: bit 0 (1) fails a segment or Receiver pass's HBM allocation (RSH_E_NOMEM), bit 1 (2) a
+ * segment pass's copies (RSH_E_DEVICE); bit 2 (4) limits both to member 1 of a multi-context call; bit 3 (8) limits
+ * both to a segment call's passes after its first, so that the call fails with files already finished (the Receiver's
+ * passes are not counted: with bit 3 set nothing fails there).
  */
 #ifndef RSYNC_HIP_DEBUG_H
 #define RSYNC_HIP_DEBUG_H

@@ -39,8 +39,10 @@ struct CoreShare {
 };
 inline int call_cores() { return CoreShare::value() > 0 ? std::min(host_cores(), CoreShare::value()) : host_cores(); }
 // multi.cpp: whether option fault_inject's bits 0 / 1 apply on this thread (bit 2 limits them to member 1 of a
-// multi-context call; tests only)
+// multi-context call, bit 3 to the passes after a call's first; tests only), and the index of the pass this
+// thread's segment call is in (segment.cpp's pass loops set it; 0 outside them)
 bool fault_here();
+int& fault_pass();
 // segment.cpp: one scan's (or pass's) stats added into a call's
 void add_scan_stats(rsh_scan_stats* to, const rsh_scan_stats& s);
 // The batched scan's resolver threads on this thread's calls: at most this many cores (0: host_cores()).  A segment

@@ -79,14 +79,25 @@ int run_members(int32_t nparts, Job* jobs, int32_t njobs, const std::vector<int6
     return RSH_OK;
 }
 
-// Fault injection (option fault_inject bit 2, tests only): bits 0 / 1 apply only to member 1 of a multi call.
+// Fault injection (option fault_inject, tests only): where bits 0 / 1 (a pass's allocation, its copies) apply.
+//   bit 2  only to member 1 of a multi call;
+//   bit 3  only from a call's second pass on, so that the files of its first pass are finished when the call fails.
+//          The pass index is the calling thread's: segment.cpp's pass loops set it.  receiver.cpp does not, so with
+//          bit 3 the faults never fire in the Receiver.
 struct MemberFaults {
     static bool& here() {
         static thread_local bool v = false;
         return v;
     }
 };
-bool fault_here() { return !(opt(OPT_FAULT_INJECT) & 4) || MemberFaults::here(); }
+int& fault_pass() {
+    static thread_local int v = 0;
+    return v;
+}
+bool fault_here() {
+    const int64_t f = opt(OPT_FAULT_INJECT);
+    return (!(f & 4) || MemberFaults::here()) && (!(f & 8) || fault_pass() >= 1);
+}
 
 namespace {
 // Member p's call on its context, with member 1's fault scope set when fault_inject asks for it.
@@ -98,6 +109,33 @@ int member_call(int32_t p, Fn&& fn) {
     MemberFaults::here() = saved;
     return rc;
 }
+
+// A segment call over several contexts: single(ctx, jobs, njobs, stats) is the single-context call, which one context
+// gets whole; otherwise the files are split by bytes_of(job), each member runs its share through it, and the members'
+// stats (where the call has any) are summed.
+template <class Job, class Single, class Bytes>
+int multi_call(rsh_ctx* const* ctxs, int32_t nctx, Job* jobs, int32_t njobs, rsh_scan_stats* stats, Single&& single,
+               Bytes&& bytes_of) {
+    if (!ctxs_ok(ctxs, nctx) || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
+    if (nctx == 1) return single(ctxs[0], jobs, njobs, stats);
+    if (stats) *stats = rsh_scan_stats{};
+    std::vector<int64_t> bytes((size_t)njobs);
+    for (int32_t f = 0; f < njobs; ++f) bytes[(size_t)f] = bytes_of(jobs[f]);
+    std::vector<rsh_scan_stats> ps((size_t)nctx);
+    const int rc = run_members(
+        nctx, jobs, njobs, bytes,
+        [&](int32_t p, Job* sub, int32_t n) {
+            return member_call(p, [&] { return single(ctxs[p], sub, n, stats ? &ps[(size_t)p] : nullptr); });
+        },
+        [](const Job& j) { return j.status; });
+    if (stats)
+        for (const rsh_scan_stats& s : ps) add_scan_stats(stats, s);
+    return rc;
+}
+
+// The Generator's and the Sender's split: by the pieces' bytes.  In the wire forms `out` and `table` are the caller's
+// pointers, so the job copies carry them.
+constexpr auto source_bytes = [](const auto& j) { return pieces_bytes(j.pieces, j.npieces); };
 }  // namespace
 
 }  // namespace rsh
@@ -124,90 +162,58 @@ int rsh_shard_files(const int64_t* bytes, int32_t nfiles, int32_t nparts, int32_
 
 int rsh_block_sums_batch_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_block_batch_job* jobs, int32_t njobs,
                                const uint8_t seed[4]) {
-    if (!ctxs_ok(ctxs, nctx) || !seed || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
-    if (nctx == 1) return rsh_block_sums_batch(ctxs[0], jobs, njobs, seed);
-    std::vector<int64_t> bytes((size_t)njobs);
-    for (int32_t f = 0; f < njobs; ++f) bytes[(size_t)f] = pieces_bytes(jobs[f].pieces, jobs[f].npieces);
-    return run_members(
-        nctx, jobs, njobs, bytes,
-        [&](int32_t p, rsh_block_batch_job* sub, int32_t n) {
-            return member_call(p, [&] { return rsh_block_sums_batch(ctxs[p], sub, n, seed); });
+    if (!seed) return RSH_E_INVAL;
+    return multi_call(
+        ctxs, nctx, jobs, njobs, nullptr,
+        [&](rsh_ctx* c, rsh_block_batch_job* sub, int32_t n, rsh_scan_stats*) {
+            return rsh_block_sums_batch(c, sub, n, seed);
         },
-        [](const rsh_block_batch_job& j) { return j.status; });
+        source_bytes);
 }
 
 int rsh_match_scan_batch_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_scan_batch_job* jobs, int32_t njobs,
                                const uint8_t seed[4], rsh_scan_stats* stats) {
-    if (!ctxs_ok(ctxs, nctx) || !seed || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
-    if (nctx == 1) return rsh_match_scan_batch(ctxs[0], jobs, njobs, seed, stats);
-    if (stats) *stats = rsh_scan_stats{};
-    std::vector<int64_t> bytes((size_t)njobs);
-    for (int32_t f = 0; f < njobs; ++f) bytes[(size_t)f] = pieces_bytes(jobs[f].pieces, jobs[f].npieces);
-    std::vector<rsh_scan_stats> ps((size_t)nctx);
-    const int rc = run_members(
-        nctx, jobs, njobs, bytes,
-        [&](int32_t p, rsh_scan_batch_job* sub, int32_t n) {
-            return member_call(p, [&] {
-                return rsh_match_scan_batch(ctxs[p], sub, n, seed, stats ? &ps[(size_t)p] : nullptr);
-            });
+    if (!seed) return RSH_E_INVAL;
+    return multi_call(
+        ctxs, nctx, jobs, njobs, stats,
+        [&](rsh_ctx* c, rsh_scan_batch_job* sub, int32_t n, rsh_scan_stats* st) {
+            return rsh_match_scan_batch(c, sub, n, seed, st);
         },
-        [](const rsh_scan_batch_job& j) { return j.status; });
-    if (stats)
-        for (const rsh_scan_stats& s : ps) add_scan_stats(stats, s);
-    return rc;
+        source_bytes);
 }
 
-// The wire forms (segment.cpp): split by the pieces' bytes as the two above; `out` and `table` are the caller's
-// pointers, so the job copies carry them.
 int rsh_block_sums_batch_wire_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_block_wire_job* jobs, int32_t njobs,
                                     const uint8_t seed[4]) {
-    if (!ctxs_ok(ctxs, nctx) || !seed || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
-    if (nctx == 1) return rsh_block_sums_batch_wire(ctxs[0], jobs, njobs, seed);
-    std::vector<int64_t> bytes((size_t)njobs);
-    for (int32_t f = 0; f < njobs; ++f) bytes[(size_t)f] = pieces_bytes(jobs[f].pieces, jobs[f].npieces);
-    return run_members(
-        nctx, jobs, njobs, bytes,
-        [&](int32_t p, rsh_block_wire_job* sub, int32_t n) {
-            return member_call(p, [&] { return rsh_block_sums_batch_wire(ctxs[p], sub, n, seed); });
+    if (!seed) return RSH_E_INVAL;
+    return multi_call(
+        ctxs, nctx, jobs, njobs, nullptr,
+        [&](rsh_ctx* c, rsh_block_wire_job* sub, int32_t n, rsh_scan_stats*) {
+            return rsh_block_sums_batch_wire(c, sub, n, seed);
         },
-        [](const rsh_block_wire_job& j) { return j.status; });
+        source_bytes);
 }
 
 int rsh_match_scan_batch_wire_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_send_job* jobs, int32_t njobs,
                                     const uint8_t seed[4], rsh_scan_stats* stats) {
-    if (!ctxs_ok(ctxs, nctx) || !seed || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
-    if (nctx == 1) return rsh_match_scan_batch_wire(ctxs[0], jobs, njobs, seed, stats);
-    if (stats) *stats = rsh_scan_stats{};
-    std::vector<int64_t> bytes((size_t)njobs);
-    for (int32_t f = 0; f < njobs; ++f) bytes[(size_t)f] = pieces_bytes(jobs[f].pieces, jobs[f].npieces);
-    std::vector<rsh_scan_stats> ps((size_t)nctx);
-    const int rc = run_members(
-        nctx, jobs, njobs, bytes,
-        [&](int32_t p, rsh_send_job* sub, int32_t n) {
-            return member_call(p, [&] {
-                return rsh_match_scan_batch_wire(ctxs[p], sub, n, seed, stats ? &ps[(size_t)p] : nullptr);
-            });
+    if (!seed) return RSH_E_INVAL;
+    return multi_call(
+        ctxs, nctx, jobs, njobs, stats,
+        [&](rsh_ctx* c, rsh_send_job* sub, int32_t n, rsh_scan_stats* st) {
+            return rsh_match_scan_batch_wire(c, sub, n, seed, st);
         },
-        [](const rsh_send_job& j) { return j.status; });
-    if (stats)
-        for (const rsh_scan_stats& s : ps) add_scan_stats(stats, s);
-    return rc;
+        source_bytes);
 }
 
 int rsh_receiver_combine_batch_multi(rsh_ctx* const* ctxs, int32_t nctx, rsh_combine_job* jobs, int32_t njobs) {
-    if (!ctxs_ok(ctxs, nctx) || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
-    if (nctx == 1) return rsh_receiver_combine_batch(ctxs[0], jobs, njobs);
-    // a file's work is its rebuilt bytes: about its replica (mostly matched) or its token stream (mostly literal)
-    std::vector<int64_t> bytes((size_t)njobs);
-    for (int32_t f = 0; f < njobs; ++f)
-        bytes[(size_t)f] = std::max<int64_t>(std::max<int64_t>(jobs[f].tokens_len, 0),
-                                             pieces_bytes(jobs[f].replica, jobs[f].nreplica));
-    return run_members(
-        nctx, jobs, njobs, bytes,
-        [&](int32_t p, rsh_combine_job* sub, int32_t n) {
-            return member_call(p, [&] { return rsh_receiver_combine_batch(ctxs[p], sub, n); });
+    return multi_call(
+        ctxs, nctx, jobs, njobs, nullptr,
+        [](rsh_ctx* c, rsh_combine_job* sub, int32_t n, rsh_scan_stats*) {
+            return rsh_receiver_combine_batch(c, sub, n);
         },
-        [](const rsh_combine_job& j) { return j.status; });
+        // a file's work is its rebuilt bytes: about its replica (mostly matched) or its token stream (mostly literal)
+        [](const rsh_combine_job& j) {
+            return std::max<int64_t>(std::max<int64_t>(j.tokens_len, 0), pieces_bytes(j.replica, j.nreplica));
+        });
 }
 
 // The split / run / merge driver with a stand-in member call (no device): part p's call records, per job, the member

@@ -37,7 +37,8 @@ enum Opt : int {
     OPT_TIME_GEN,          // 1: rsh_block_sums_device's K1 records timing events (rsh_debug_kernel_ms)
     OPT_BATCH_WARM,        // rsh_ctx_create pre-sizes the batched scan's state for this many 128 MiB files (0: none)
     OPT_FAULT_INJECT,      // tests only: bit 0 a segment / Receiver pass's HBM allocation fails, bit 1 a segment's copies fail,
-                           // bit 2 bits 0 / 1 only on member 1 of a multi-context call (multi.cpp)
+                           // bit 2 bits 0 / 1 only on member 1 of a multi-context call, bit 3 only from a segment call's
+                           // second pass on (multi.cpp)
     OPT_TOKENS_SPAN,       // rsh_tokens_write_*device / _kept: stream bytes per span descriptor
     OPT_TOKENS_PIECE,      // ... bytes per pinned staging buffer (two of them: one filled while the other is copied out)
     OPT_SUMS_PIECE,        // rsh_sums_*_device / rsh_*_batch_wire: table bytes per pinned staging piece (one launch each)

@@ -205,3 +205,50 @@ def test_segment_failure_marks_every_unfinished_file(ctx, rsh_opt, fault):
     rsh_opt("fault_inject", 0)
     sums = ctx.block_sums_batch([([f], h) for f, h in zip(files, heads)], SEED)
     assert all(np.array_equal(w, ow) and np.array_equal(s, os_) for (w, s), (ow, os_) in zip(sums, tabs))
+
+
+@pytest.mark.parametrize("fault", [1 | 8, 2 | 8])
+def test_segment_failure_after_the_first_pass_keeps_finished_files(ctx, rsh_opt, fault):
+    """The same contract when the failure comes later (fault_inject bit 3: bits 0 / 1 apply from a call's second pass
+    on).  At a budget of 3 * 40 * B the five files go in the passes {0,1}, {2,3}, {4} (each aligned file is at most
+    20736 B); the results show that split: files 0 and 1 are finished -- RSH_OK with the oracle's sums, events, counts
+    and MD5 -- and files 2 to 4 carry the call's code, which the call returns.  Every valid file of the Sender call
+    still has its MD5.  With the option cleared the same calls succeed in full."""
+    B, dl = 512, 2
+    bases = [O.splitmix(40 * B + 9 * k, 77 + k) for k in range(5)]
+    srcs = []
+    for k, b in enumerate(bases):
+        s = b.copy()
+        s[(3 + k) * B:(5 + k) * B] = O.splitmix(2 * B, 177 + k)
+        srcs.append(s)
+    heads = [R.header_make(B, dl, f.size) for f in bases]
+    tabs = [O.generator(f, O.header(B, dl, f.size), SEED) for f in bases]
+    sent = [O.sender(s, O.header(B, dl, f.size), w, st, SEED) for s, f, (w, st) in zip(srcs, bases, tabs)]
+    gen = [([f], h) for f, h in zip(bases, heads)]
+    snd = [([s], h, w, st) for s, h, (w, st) in zip(srcs, heads, tabs)]
+    want = R.RSH_E_NOMEM if fault & 1 else R.RSH_E_DEVICE
+
+    def sums_ok(got, i):
+        return np.array_equal(got[i][0], tabs[i][0]) and np.array_equal(got[i][1], tabs[i][1])
+
+    def sender_ok(o, i):
+        oev, ofm, olit, omat, _ = sent[i]
+        return R.events_as_tuples(o[0], B) == [tuple(e) for e in oev] and o[1:4] == (ofm, olit, omat)
+
+    rsh_opt("segment_bytes", 3 * 40 * B)
+    rsh_opt("fault_inject", fault)
+    st = []
+    sums = ctx.block_sums_batch(gen, SEED, statuses=st)
+    assert st == [want, 0, 0, want, want, want], st
+    assert sums_ok(sums, 0) and sums_ok(sums, 1)
+    st = []
+    out, _ = ctx.match_scan_batch(snd, SEED, statuses=st)
+    assert st == [want] and [o[4] for o in out] == [0, 0, want, want, want], (st, [o[4] for o in out])
+    assert sender_ok(out[0], 0) and sender_ok(out[1], 1)
+    assert [o[1] for o in out] == [s[1] for s in sent]  # the MD5s, failed files included
+    rsh_opt("fault_inject", 0)
+    st = []
+    sums = ctx.block_sums_batch(gen, SEED, statuses=st)
+    assert st == [0] * 6 and all(sums_ok(sums, i) for i in range(5))
+    out, _ = ctx.match_scan_batch(snd, SEED, statuses=st)
+    assert st == [0] and all(o[4] == 0 and sender_ok(o, i) for i, o in enumerate(out))

@@ -353,3 +353,52 @@ def test_wire_failure_marks_every_unfinished_file(ctx, rsh_opt, seg, fault):
     assert [r[1] for r in res] == seg["wire"][:5]
     out, _ = ctx.match_scan_batch_wire(snd, SEED)
     assert [o[6] for o in out] == seg["tokens"][:5]
+
+
+@pytest.mark.parametrize("fault", [1 | 8, 2 | 8])
+def test_wire_failure_after_the_first_pass_keeps_finished_files(ctx, rsh_opt, fault):
+    """The failure comes in the second pass (fault_inject bit 3: bits 0 / 1 apply from a call's second pass on).  At a
+    budget of 3 * 40 * B the five files go in the passes {0,1}, {2,3}, {4} (each aligned file is at most 20736 B); the
+    results show that split: files 0 and 1 are finished -- RSH_OK in status and out_status with the oracle's Generator
+    bytes, events, counts, MD5 and token stream -- and files 2 to 4 carry the call's code in both, their stream unwritten.
+    Every valid file of the Sender call still has its MD5; the call returns the code.  With the option cleared the same
+    calls succeed in full."""
+    B, dl = 512, 2
+    bases = [O.splitmix(40 * B + 9 * k, 77 + k) for k in range(5)]
+    srcs = []
+    for k, b in enumerate(bases):
+        s = b.copy()
+        s[(3 + k) * B:(5 + k) * B] = O.splitmix(2 * B, 177 + k)
+        srcs.append(s)
+    heads = [R.header_make(B, dl, f.size) for f in bases]
+    wire, sent, toks = [], [], []
+    for f, s, h in zip(bases, srcs, heads):
+        oh = O.header(B, dl, f.size)
+        ow, os_ = O.generator(f, oh, SEED)
+        wire.append(SC.oracle_wire(h, ow, os_))
+        oev, ofm, olit, omat, _ = O.sender(s, oh, ow, os_, SEED)
+        sent.append(([tuple(e) for e in oev], ofm, olit, omat))
+        toks.append(O.tokens(s, oev, ofm))
+    gen = [([f], h) for f, h in zip(bases, heads)]
+    snd = [([s], h, np.frombuffer(w, np.uint8)[16:]) for s, h, w in zip(srcs, heads, wire)]
+    want = R.RSH_E_NOMEM if fault & 1 else R.RSH_E_DEVICE
+
+    def sender_ok(o, i):
+        return (R.events_as_tuples(o[0], B), o[1], o[2], o[3]) == sent[i] and o[4:7] == (0, 0, toks[i])
+
+    rsh_opt("segment_bytes", 3 * 40 * B)
+    rsh_opt("fault_inject", fault)
+    st = []
+    res = ctx.block_sums_batch_wire(gen, SEED, statuses=st)
+    assert st == [want] and [r[0] for r in res] == [0, 0, want, want, want], (st, [r[0] for r in res])
+    assert [r[1] for r in res] == wire[:2] + [None] * 3
+    out, _ = ctx.match_scan_batch_wire(snd, SEED, statuses=st)
+    assert st == [want], st
+    assert [(o[4], o[5], o[6]) for o in out[2:]] == [(want, want, None)] * 3, [o[4:6] for o in out]
+    assert sender_ok(out[0], 0) and sender_ok(out[1], 1)
+    assert [o[1] for o in out] == [s[1] for s in sent]  # the MD5s, failed files included
+    rsh_opt("fault_inject", 0)
+    res = ctx.block_sums_batch_wire(gen, SEED, statuses=st)
+    assert st == [0] and [r[1] for r in res] == wire
+    out, _ = ctx.match_scan_batch_wire(snd, SEED, statuses=st)
+    assert st == [0] and all(sender_ok(o, i) for i, o in enumerate(out))
