@@ -178,6 +178,11 @@ int rsh_tokens_write(const uint8_t* src, const rsh_event* ev, int64_t n_ev, cons
  * no source. */
 int rsh_tokens_write_device(rsh_ctx* ctx, const void* d_src, int64_t n, const rsh_event* ev, int64_t n_ev,
                             const uint8_t file_md5[16], int64_t from, uint8_t* out, int64_t len);
+/* The same bytes, after the same checks, into device memory [d_out, d_out + len) at any byte alignment, trailer
+ * included: the kernel writes straight to d_out (no staging, no host copy), so that a Receiver on the same device
+ * takes the stream where it lies (rsh_receiver_combine_resident). */
+int rsh_tokens_frame_device(rsh_ctx* ctx, const void* d_src, int64_t n, const rsh_event* ev, int64_t n_ev,
+                            const uint8_t file_md5[16], int64_t from, void* d_out, int64_t len);
 /* The same over the source the context's last single-file scan left in HBM: rsh_match_scan (block_length > 0),
  * rsh_match_scan_file below option file_tile_above (a new file included) and rsh_match_scan_pieces when resident
  * record it; every other call that uses the context's buffers, rsh_ctx_trim and a failed scan drop it (the lifetime of
@@ -428,6 +433,14 @@ int rsh_receiver_combine(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len
 int rsh_receiver_combine_device(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, const rsh_header* h,
                                 const void* d_replica, int64_t replica_len, int32_t defer_write, void* d_target,
                                 int64_t target_cap, rsh_combine_result* out);
+/* The stream in device memory too (a local transfer: Sender, Generator and Receiver on one device): the token walk
+ * runs on the device and only its run list comes down -- no stream byte crosses PCIe; literal runs are placed from
+ * the raw stream by a kernel.  Results and statuses are those of the form above for the same bytes (of several errors
+ * the first offending token in stream order decides).  flags: 0, or RSH_COMBINE_NO_MD5. */
+#define RSH_COMBINE_NO_MD5 1   /* out->md5 zeroed: the caller digests the bytes it downloads anyway */
+int rsh_receiver_combine_resident(rsh_ctx* ctx, const void* d_tokens, int64_t tokens_len, const rsh_header* h,
+                                  const void* d_replica, int64_t replica_len, int32_t defer_write, void* d_target,
+                                  int64_t target_cap, int32_t flags, rsh_combine_result* out);
 
 /* ---- a segment's Receiver from host memory (Receiver.receiveFiles, Receiver.java:1145-1263: combineDataToFile
  * :459-556 and isRemoteAndLocalFileIdentical :824-842 for each file in turn) ----

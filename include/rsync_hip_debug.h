@@ -7,7 +7,7 @@
  * Tests force rare paths with them; a few are tunables: k1_gather, k1_shift,
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
- * fault_inject, tokens_span, tokens_piece, sums_piece.
+ * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs.
  *
  * fault_inject is a bit set: bit 0 (1) fails a segment or Receiver pass's HBM allocation (RSH_E_NOMEM), bit 1 (2) a
  * segment pass's copies (RSH_E_DEVICE); bit 2 (4) limits both to member 1 of a multi-context call; bit 3 (8) limits
@@ -76,6 +76,28 @@ int rsh_debug_tokens_selftest(const uint8_t* src, int64_t n, const rsh_event* ev
  * bytes: RSH_E_INVAL unless chunk_count * (4 + digest_length)) -> weak, strong.  *n_desc: the descriptor count. */
 int rsh_debug_sums_selftest(int32_t unframe, const rsh_header* h, int32_t* weak, uint8_t* strong, uint8_t* wire,
                             int64_t len, int64_t span, int64_t* n_desc);
+
+/* The resident Receiver's token walk, token_scan_kernel: one pass from stream offset `from` writes at
+ * most cap records (1 .. 2^24).  ctx == NULL: `tokens` is host memory and a host stand-in runs the kernel's lanes one
+ * after another; otherwise `tokens` is device memory and the kernel runs.  *status: 1 the stream's putInt(0) was
+ * reached (*pos: the byte after it), 0 the list is full (*pos: the first token not listed; call again from there),
+ * RSH_E_INVAL the stream is cut short at the token at *pos. */
+typedef struct {
+    int64_t pos;    /* stream offset of the run's first header */
+    int32_t kind;   /* RSH_EV_LITERAL / RSH_EV_MATCH */
+    int32_t value;  /* LITERAL: the tokens' length; MATCH: the first block index */
+    int64_t count;  /* tokens: equal lengths, or consecutive indices */
+} rsh_token_run;
+int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
+                                   rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status);
+
+/* token_unframe_kernel on one literal run: `count` >= 2 tokens of T >= 16 bytes whose first header is at stream offset
+ * pos (else RSH_E_INVAL), their data placed at out[0, count * T) in spans of `span` bytes (0: option tokens_span).
+ * ctx == NULL: host pointers, a host stand-in of the kernel; *lo, *hi: the lowest stream offset it loaded (may be
+ * negative: the aligned quantity that holds the first byte) and the one after the highest.  Otherwise device pointers
+ * and the kernel (lo, hi untouched).  *n_desc: the descriptor count. */
+int rsh_debug_untokens_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t pos, int32_t T,
+                                int64_t count, uint8_t* out, int64_t span, int64_t* n_desc, int64_t* lo, int64_t* hi);
 
 #ifdef __cplusplus
 }

@@ -336,6 +336,15 @@ hipError_t launch_gather_ops_variant(int v, const GatherOp* ops, uint32_t n, hip
 // dst_on_host: the spans' destinations are pinned host memory (plain stores).
 struct TokSpan;
 hipError_t launch_token_frame(const TokSpan* spans, uint32_t n, uint32_t max_len, bool dst_on_host, hipStream_t s);
+// The Receiver's side of a stream in HBM (device_tokens.hip, token_scan.h).  Walk: one wave from stream offset `from`
+// writes at most cap run records and the TokScanOut (both device memory).  Unframe: literal runs' spans (device or
+// pinned host memory) placed from the raw stream; max_len: the longest span's bytes.
+struct TokRun;
+struct TokScanOut;
+struct UntokSpan;
+hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
+                             hipStream_t s);
+hipError_t launch_token_unframe(const UntokSpan* spans, uint32_t n, uint32_t max_len, hipStream_t s);
 hipError_t launch_warm_tokens(hipStream_t s);
 // The checksum table between SoA and wire form (device_sums.hip, sums_frame.h): spans in device or pinned host
 // memory; max_len: the longest span's bytes.

@@ -1,10 +1,15 @@
 // device_tokens.hip -- token_frame_kernel: the Sender's channel bytes (length headers, literal bytes, match integers)
 // written from a source in HBM, one workgroup per 64 KiB of a span descriptor (token_frame.h has the layout, the memory rules
 // and the per-quantity arithmetic; tokens.cpp plans the spans and owns the entry points).
+// token_scan_kernel and token_unframe_kernel: the Receiver's side of a stream that lies in HBM -- the token walk as a
+// run list, one wave proving up to 64 literal or 1024 match tokens per memory round trip, and the literal runs placed
+// from the raw stream, the framer's mirror on the framer's grid (token_scan.h; receiver.cpp plans and owns the entry
+// points).
 #include <hip/hip_runtime.h>
 
 #include "device.h"
 #include "token_frame.h"
+#include "token_scan.h"
 
 namespace rsh {
 
@@ -94,6 +99,109 @@ hipError_t launch_token_frame(const TokSpan* spans, uint32_t n, uint32_t max_len
     const dim3 grid(n, (max_len + kTokBlock - 1) / kTokBlock);
     if (dst_on_host) hipLaunchKernelGGL(token_frame_kernel<false>, grid, dim3(kTokThreads), 0, s, spans);
     else hipLaunchKernelGGL(token_frame_kernel<true>, grid, dim3(kTokThreads), 0, s, spans);
+    return hipGetLastError();
+}
+
+// D quantities of an unframe span, `step` bytes apart from o + k on: their loads first, then the stores.  A lane's
+// loads never depend on a lane's own condition: a quantity that holds no needed byte is a second read of one that does
+// (no other memory touched).  The third quantity is needed only where a header falls in the last bytes of the second
+// (one target quantity in ~2700 at T = 8192), so the wave reads it -- every lane, by the same rule -- only when one of
+// its lanes needs it: with three loads per quantity always, 1 GiB took 0.494 ms against the gather's 0.345
+// (profiles/untokens/kbench_three_loads.log).
+template <int D>
+__device__ __forceinline__ void unlit_quantities(const UntokSpan& sp, uint8_t* o, uint32_t j0, uint32_t k, uint32_t step) {
+    UntokQ P[D];
+    Q16 q0[D], q1[D], q2[D];
+    uint32_t sh[D];
+    const uint8_t* a2[D];
+    bool third = false, gap = false;
+#pragma unroll
+    for (int u = 0; u < D; ++u) {
+        P[u] = untok_plan(sp.T, j0 + k + u * step);
+        const uintptr_t s = reinterpret_cast<uintptr_t>(sp.src + P[u].s);
+        const uint8_t* a0 = reinterpret_cast<const uint8_t*>(s & ~(uintptr_t)15);
+        sh[u] = (uint32_t)(s & 15);
+        const uint32_t e = untok_extent(sh[u], P[u].a);
+        const uint32_t o1 = e >= 16 ? 16 : 0;
+        q0[u] = tok_load(a0);
+        q1[u] = tok_load(a0 + o1);
+        a2[u] = a0 + (e >= 32 ? 32 : o1);
+        third = third || e >= 32;
+        gap = gap || P[u].a < 16;
+    }
+    if (!__any(gap)) {  // no token boundary in any of the wave's quantities (seven wave-rows in eight at T = 8192)
+#pragma unroll
+        for (int u = 0; u < D; ++u) tok_store<true>(o + k + u * step, tok_funnel(q0[u], q1[u], sh[u]));
+        return;
+    }
+    if (__any(third)) {  // (wave-uniform)
+#pragma unroll
+        for (int u = 0; u < D; ++u) q2[u] = tok_load(a2[u]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < D; ++u) q2[u] = q1[u];
+    }
+#pragma unroll
+    for (int u = 0; u < D; ++u) tok_store<true>(o + k + u * step, untok_merge(q0[u], q1[u], q2[u], sh[u], P[u].a));
+}
+
+// The framer's grid: (span, kTokBlock bytes of it), kTokThreads threads.
+__global__ __launch_bounds__(kTokThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void token_unframe_kernel(const UntokSpan* __restrict__ spans) {
+    const UntokSpan whole = spans[blockIdx.x];
+    const uint32_t at = blockIdx.y * kTokBlock;
+    if (at >= whole.len) return;
+    const UntokSpan sp = untok_block(whole, at, kTokBlock);
+    uint8_t* const d = sp.dst;
+    const uint32_t len = sp.len, tid = threadIdx.x;
+    uint32_t head = (uint32_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15);
+    if (head > len) head = len;
+    const uint32_t body = (len - head) & ~15u, tail = len - head - body;
+    if (tid < head + tail) {
+        typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
+        typedef uint8_t __attribute__((address_space(1))) * GlobalByteOut;
+        const uint32_t x = tid < head ? tid : body + tid;
+        ((GlobalByteOut)(uintptr_t)d)[x] = ((GlobalByte)(uintptr_t)sp.src)[untok_byte_off(sp.T, sp.r0 + x)];
+    }
+    uint8_t* const o = d + head;
+    const uint32_t j0 = sp.r0 + head, step = 16 * kTokThreads;
+    uint32_t k = 16 * tid;
+    for (; k + (kTokDepth - 1) * step < body; k += kTokDepth * step) unlit_quantities<kTokDepth>(sp, o, j0, k, step);
+    for (; k < body; k += step) unlit_quantities<1>(sp, o, j0, k, step);
+}
+
+hipError_t launch_token_unframe(const UntokSpan* spans, uint32_t n, uint32_t max_len, hipStream_t s) {
+    if (n == 0 || max_len == 0) return hipSuccess;
+    const dim3 grid(n, (max_len + kTokBlock - 1) / kTokBlock);
+    hipLaunchKernelGGL(token_unframe_kernel, grid, dim3(kTokThreads), 0, s, spans);
+    return hipGetLastError();
+}
+
+// One wave walks the stream from `from` (token_scan.h tok_scan_walk): every lane runs the same control flow over
+// wave-uniform values, lane 0 stores the records.
+__global__ __launch_bounds__(kScanLanes) void token_scan_kernel(const uint8_t* __restrict__ tokens, int64_t len, int64_t from,
+                                                               TokRun* __restrict__ runs, int64_t cap, TokScanOut* __restrict__ out) {
+    typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
+    const GlobalByte base = (GlobalByte)(uintptr_t)tokens;
+    const uint32_t lane = threadIdx.x;
+    auto ld = [&](int64_t off) -> int32_t {
+        const GlobalByte p = base + off;
+        return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+    };
+    auto head = [&](int64_t pos) -> int32_t { return __builtin_amdgcn_readfirstlane(ld(pos)); };
+    auto round = [&](int64_t pos, int32_t v) -> int64_t {
+        const uint32_t per = v > 0 ? 1u : kScanMatchPer;
+        const uint32_t c = tok_scan_lane(ld, pos, len, v, lane);
+        const unsigned long long full = __ballot(c == per);
+        const uint32_t L = full == ~0ull ? kScanLanes : (uint32_t)__builtin_ctzll(~full);  // leading full lanes
+        const uint32_t part = L < kScanLanes ? (uint32_t)__shfl((int)c, (int)L) : 0u;    // the first other lane's ints
+        return (int64_t)__builtin_amdgcn_readfirstlane((int)(per * L + part));
+    };
+    tok_scan_walk(head, round, len, from, runs, cap, lane == 0, out);
+}
+
+hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(token_scan_kernel, dim3(1), dim3(kScanLanes), 0, s, tokens, len, from, runs, cap, out);
     return hipGetLastError();
 }
 

@@ -6,6 +6,9 @@
 // upload, replica blocks as device-to-device gathers (one launch for the whole file).  The digest the
 // Receiver compares with the Sender's file MD5 (:824-842) is one serial MD5 chain over the rebuilt file;
 // it runs on the host while the next piece of the file comes back over PCIe.
+//
+// rsh_receiver_combine_resident takes the stream itself from HBM: there the walk runs on the device and the host
+// plans runs of tokens (the second half of this file).
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -14,6 +17,8 @@
 #include "host_md5.h"
 #include "md5_mb.h"
 #include "options.h"
+#include "rsync_hip_debug.h"
+#include "token_scan.h"
 
 namespace rsh {
 namespace {
@@ -437,12 +442,325 @@ int combine_passes(rsh_ctx* c, rsh_combine_job* jobs, std::vector<RFile>& files,
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The Receiver over a stream in HBM (rsh_receiver_combine_resident): the walk runs on the device and hands the host a
+// run list (token_scan.h); the host runs plan_combine's control flow once per run instead of once per token, and the
+// bytes move in one gather launch (replica block runs, single or short literal tokens) and one unframe launch (literal
+// runs from the raw stream).  No stream byte crosses PCIe.
+// ------------------------------------------------------------------------------------------------
+struct RunPiece {
+    bool literal;
+    int64_t off;    // replica offset, or the stream offset of the literal run's first header
+    int64_t len;    // target bytes
+    int32_t T;      // literal: the tokens' length
+    int64_t count;  // literal: tokens
+};
+
+// plan_combine over runs.  The state persists from one run list to the next (the walk resumes where the list was full);
+// a run's errors are reported as the host walk would meet them, token by token in stream order.
+struct RunPlan {
+    const rsh_header& h;
+    const bool have_replica;
+    const int64_t replica_len;
+    bool deferrable;
+    int32_t expected = 0;
+    std::vector<RunPiece> pieces;  // in target order
+    int64_t target_len = 0, literal = 0, matched = 0, intact_len = 0;
+    bool intact = false;
+    RunPlan(const rsh_header& hh, bool rep, int64_t rep_len, bool defer)
+        : h(hh), have_replica(rep), replica_len(rep_len), deferrable(defer && rep) {}
+    // blocks [first, first + cnt), all below chunk_count: only the last one can be the short block
+    int64_t blocks_bytes(int64_t first, int64_t cnt) const {
+        return (cnt - 1) * (int64_t)h.block_length + block_size((int32_t)(first + cnt - 1), h);
+    }
+    int add_blocks(int64_t first, int64_t cnt) {
+        if (cnt <= 0) return RSH_OK;
+        const int64_t off = first * h.block_length, len = blocks_bytes(first, cnt);
+        if (off + len > replica_len) return RSH_E_INVAL;  // the blocks' ends ascend: the last one decides
+        RunPiece* last = pieces.empty() ? nullptr : &pieces.back();
+        if (last && !last->literal && last->off + last->len == off) last->len += len;
+        else pieces.push_back(RunPiece{false, off, len, 0, 0});
+        target_len += len;
+        return RSH_OK;
+    }
+    int flush_deferred() {
+        deferrable = false;
+        return add_blocks(0, expected);
+    }
+    int match_run(int64_t first, int64_t cnt) {
+        const int64_t valid = std::min(cnt, std::max<int64_t>(0, (int64_t)h.chunk_count - first));
+        if (valid == 0 || h.block_length == 0) return RSH_E_PROTOCOL;  // the run's first token already
+        if (have_replica) {
+            matched += blocks_bytes(first, valid);
+            int64_t left = valid;
+            if (deferrable) {
+                if (first == expected) {  // consecutive indices: every token of the run is the expected one
+                    expected += (int32_t)valid;
+                    left = 0;
+                } else {
+                    const int rc = flush_deferred();
+                    if (rc != RSH_OK) return rc;
+                }
+            }
+            const int rc = add_blocks(first, left);
+            if (rc != RSH_OK) return rc;
+        }
+        return valid < cnt ? RSH_E_PROTOCOL : RSH_OK;  // the first index past the table comes after the valid ones
+    }
+    int literal_run(int64_t pos, int32_t T, int64_t cnt) {
+        if (deferrable) {
+            const int rc = flush_deferred();
+            if (rc != RSH_OK) return rc;
+        }
+        pieces.push_back(RunPiece{true, pos, cnt * (int64_t)T, T, cnt});
+        target_len += cnt * (int64_t)T;
+        literal += cnt * (int64_t)T;
+        return RSH_OK;
+    }
+    int add(const TokRun& r) {
+        return r.kind == RSH_EV_LITERAL ? literal_run(r.pos, r.v, r.count) : match_run(r.v, r.count);
+    }
+    int finish() {  // after putInt(0) (:529-545)
+        if (deferrable && expected != h.chunk_count) {
+            const int rc = flush_deferred();
+            if (rc != RSH_OK) return rc;
+        }
+        if (deferrable) {
+            if (expected > 0) {
+                intact_len = blocks_bytes(0, expected);
+                if (intact_len > replica_len) return RSH_E_INVAL;
+            }
+            intact = true;
+        }
+        return RSH_OK;
+    }
+};
+
+// Which literal runs token_unframe_kernel takes: at most one header in a 16-byte quantity, and more than one token
+// (a single token is a plain range).
+bool unframe_takes(int32_t T, int64_t count) { return T >= 16 && count >= 2; }
+
+int64_t untok_span_bytes(int64_t forced = 0) {
+    return std::min<int64_t>(std::max<int64_t>(forced > 0 ? forced : opt(OPT_TOKENS_SPAN), 16), kTokMaxSpan);
+}
+
+// The walk over host pointers: token_scan_kernel's lanes one after another.
+void scan_host(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out) {
+    auto ld = [&](int64_t off) { return get_int(tokens + off); };
+    auto round = [&](int64_t pos, int32_t v) -> int64_t {
+        const uint32_t per = v > 0 ? 1u : kScanMatchPer;
+        int64_t m = 0;
+        for (uint32_t lane = 0; lane < kScanLanes; ++lane) {
+            const uint32_t c = tok_scan_lane(ld, pos, len, v, lane);
+            m += c;
+            if (c != per) break;
+        }
+        return m;
+    };
+    tok_scan_walk(ld, round, len, from, runs, cap, true, out);
+}
+
+// token_unframe_kernel's work on one span, over host pointers: the same workgroup split, the same bytes one by one
+// around the 16-byte boundaries of dst, the same quantities from the same aligned loads.  [*lo, *hi): what was loaded.
+void run_unspan_host(const UntokSpan& whole, const uint8_t** lo, const uint8_t** hi) {
+    constexpr uint32_t kBlock = 64 << 10;  // device_tokens.hip kTokBlock
+    auto loaded = [&](const uint8_t* a, size_t n) {
+        if (!*lo || a < *lo) *lo = a;
+        if (!*hi || a + n > *hi) *hi = a + n;
+    };
+    for (uint32_t at = 0; at < whole.len; at += kBlock) {
+        const UntokSpan sp = untok_block(whole, at, kBlock);
+        uint8_t* const d = sp.dst;
+        const uint32_t len = sp.len;
+        const uint32_t head = std::min<uint32_t>(len, (uint32_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15));
+        const uint32_t body = (len - head) & ~15u;
+        auto byte_at = [&](uint32_t x) {
+            const uint8_t* s = sp.src + untok_byte_off(sp.T, sp.r0 + x);
+            loaded(s, 1);
+            d[x] = *s;
+        };
+        for (uint32_t x = 0; x < head; ++x) byte_at(x);
+        for (uint32_t x = head + body; x < len; ++x) byte_at(x);
+        const uint32_t j0 = sp.r0 + head;
+        for (uint32_t k = 0; k < body; k += 16) {
+            const UntokQ P = untok_plan(sp.T, j0 + k);
+            const uintptr_t s = reinterpret_cast<uintptr_t>(sp.src + P.s);
+            const uint8_t* a0 = reinterpret_cast<const uint8_t*>(s & ~(uintptr_t)15);
+            const uint32_t sh = (uint32_t)(s & 15), e = untok_extent(sh, P.a);
+            Q16 q[3];
+            for (uint32_t i = 0; i < 3; ++i) {
+                const uint8_t* a = a0 + (e >= 16 * i ? 16 * i : e >= 16 ? 16 : 0);  // (the kernel's re-read)
+                memcpy(&q[i], a, 16);
+                loaded(a, 16);
+            }
+            const Q16 r = untok_merge(q[0], q[1], q[2], sh, P.a);
+            memcpy(d + head + k, &r, 16);
+        }
+    }
+}
+
+// One launch of the walk into c->tok_runs, its TokScanOut and records copied to c->h_runs: two small downloads.
+int scan_device_runs(rsh_ctx* c, const uint8_t* d_tokens, int64_t len, int64_t from, int64_t cap, TokScanOut* out,
+                     const TokRun** runs) {
+    constexpr size_t kHead = 32;  // the TokScanOut, then the records
+    static_assert(sizeof(TokScanOut) <= kHead, "TokScanOut");
+    RSH_HIP(c->tok_runs.ensure(kHead + (size_t)cap * sizeof(TokRun)));
+    RSH_HIP(c->h_runs.ensure(kHead + (size_t)cap * sizeof(TokRun)));
+    uint8_t* d = c->tok_runs.as<uint8_t>();
+    uint8_t* hp = c->h_runs.as<uint8_t>();
+    RSH_HIP(launch_token_scan(d_tokens, len, from, reinterpret_cast<TokRun*>(d + kHead), cap,
+                              reinterpret_cast<TokScanOut*>(d), c->stream));
+    RSH_HIP(hipMemcpyAsync(hp, d, kHead, hipMemcpyDeviceToHost, c->stream));
+    RSH_HIP(hipStreamSynchronize(c->stream));
+    memcpy(out, hp, sizeof(TokScanOut));
+    if (out->n < 0 || out->n > cap) return RSH_E_DEVICE;
+    if (out->n > 0) {
+        RSH_HIP(hipMemcpyAsync(hp + kHead, d + kHead, (size_t)out->n * sizeof(TokRun), hipMemcpyDeviceToHost, c->stream));
+        RSH_HIP(hipStreamSynchronize(c->stream));
+    }
+    *runs = reinterpret_cast<const TokRun*>(hp + kHead);
+    return RSH_OK;
+}
+
+// The launches of a resident plan: replica ranges and the literal runs the unframe kernel does not take as gather ops,
+// the other literal runs as unframe spans.
+int place_resident(rsh_ctx* c, const RunPlan& P, const uint8_t* d_tokens, const uint8_t* d_replica, uint8_t* d_target) {
+    std::vector<GatherOp> ops;
+    std::vector<UntokSpan> spans;
+    const int64_t span = untok_span_bytes();
+    int64_t t = 0;
+    auto range = [&](const uint8_t* src, uint8_t* dst, int64_t len) {
+        for (int64_t o = 0; o < len; o += kOpPiece) ops.push_back(GatherOp{src + o, dst + o, std::min<int64_t>(kOpPiece, len - o)});
+    };
+    for (const RunPiece& p : P.pieces) {
+        if (!p.literal) range(d_replica + p.off, d_target + t, p.len);
+        else if (unframe_takes(p.T, p.count)) untok_plan_run(d_tokens + p.off, (uint32_t)p.T, p.count, d_target + t, span, spans);
+        else
+            for (int64_t k = 0; k < p.count; ++k) range(d_tokens + p.off + k * ((int64_t)p.T + 4) + 4, d_target + t + k * p.T, p.T);
+        t += p.len;
+    }
+    if (ops.size() > (size_t)INT32_MAX || spans.size() > (size_t)INT32_MAX) return RSH_E_INVAL;
+    if (!ops.empty()) {
+        RSH_HIP(c->h_pos.ensure(ops.size() * sizeof(GatherOp)));  // read by the kernel from pinned memory
+        memcpy(c->h_pos.p, ops.data(), ops.size() * sizeof(GatherOp));
+        int64_t bytes = 0;
+        for (const GatherOp& o : ops) bytes += o.len;
+        RSH_HIP(launch_gather_ops(c->h_pos.as<GatherOp>(), (uint32_t)ops.size(), c->stream, bytes / (int64_t)ops.size()));
+    }
+    if (!spans.empty()) {
+        RSH_HIP(c->h_untok.ensure(spans.size() * sizeof(UntokSpan)));
+        memcpy(c->h_untok.p, spans.data(), spans.size() * sizeof(UntokSpan));
+        uint32_t max_len = 0;
+        for (const UntokSpan& s : spans) max_len = std::max(max_len, s.len);
+        RSH_HIP(launch_token_unframe(c->h_untok.as<UntokSpan>(), (uint32_t)spans.size(), max_len, c->stream));
+    }
+    return RSH_OK;
+}
+
 }  // namespace
 }  // namespace rsh
 
 using namespace rsh;
 
 extern "C" {
+
+int rsh_receiver_combine_resident(rsh_ctx* ctx, const void* d_tokens, int64_t tokens_len, const rsh_header* h,
+                                  const void* d_replica, int64_t replica_len, int32_t defer_write, void* d_target,
+                                  int64_t target_cap, int32_t flags, rsh_combine_result* out) {
+    if (!ctx || !h || !out || !d_tokens || tokens_len < 0 || replica_len < 0 || target_cap < 0) return RSH_E_INVAL;
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    const uint8_t* tok = static_cast<const uint8_t*>(d_tokens);
+    const uint8_t* rep = static_cast<const uint8_t*>(d_replica);
+    uint8_t* tgt = static_cast<uint8_t*>(d_target);
+    // the walk and the plan: every run is validated before anything reads through it
+    RunPlan P(*h, d_replica != nullptr, replica_len, defer_write != 0);
+    const int64_t cap = std::min<int64_t>(std::max<int64_t>(opt(OPT_TOKENS_RUNS), 1), 1 << 24);
+    TokScanOut so{0, 0, TOK_SCAN_MORE, 0};
+    while (so.status == TOK_SCAN_MORE) {
+        const TokRun* runs = nullptr;
+        const int rc = scan_device_runs(ctx, tok, tokens_len, so.pos, cap, &so, &runs);
+        if (rc != RSH_OK) return rc;
+        for (int64_t i = 0; i < so.n; ++i) {
+            const int rp = P.add(runs[i]);
+            if (rp != RSH_OK) return rp;
+        }
+    }
+    if (so.status != TOK_SCAN_END) return RSH_E_INVAL;  // cut short, after every token before the cut was planned
+    const int rf = P.finish();
+    if (rf != RSH_OK) return rf;
+    out->tokens_used = so.pos;
+    out->target_len = P.intact ? 0 : P.target_len;
+    out->literal = P.literal;
+    out->matched = P.matched;
+    out->intact = P.intact ? 1 : 0;
+    out->reserved = 0;
+    memset(out->md5, 0, 16);
+    if (!P.intact && P.target_len > target_cap) return RSH_E_NOSPACE;
+    if (!P.intact && P.target_len > 0 && !d_target) return RSH_E_INVAL;
+    if (!P.intact) {
+        const int g = place_resident(ctx, P, tok, rep, tgt);
+        if (g != RSH_OK) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return g;
+        }
+    }
+    if (flags & RSH_COMBINE_NO_MD5) {
+        RSH_HIP(hipStreamSynchronize(ctx->stream));  // the descriptors are read until the launches are done
+        return RSH_OK;
+    }
+    return md5_device(ctx, P.intact ? rep : tgt, P.intact ? P.intact_len : P.target_len, out->md5);
+}
+
+int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
+                                   rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status) {
+    static_assert(sizeof(rsh_token_run) == sizeof(TokRun), "rsh_token_run is TokRun");
+    if (!tokens || tokens_len < 0 || from < 0 || from > tokens_len || cap < 1 || cap > (1 << 24) || !runs || !n_runs ||
+        !pos || !status)
+        return RSH_E_INVAL;
+    TokScanOut so;
+    if (ctx) {
+        RSH_CLAIM(ctx);
+        RSH_HIP(hipSetDevice(ctx->device));
+        const TokRun* got = nullptr;
+        const int rc = scan_device_runs(ctx, tokens, tokens_len, from, cap, &so, &got);
+        if (rc != RSH_OK) return rc;
+        memcpy(runs, got, (size_t)so.n * sizeof(TokRun));
+    } else {
+        scan_host(tokens, tokens_len, from, reinterpret_cast<TokRun*>(runs), cap, &so);
+    }
+    *n_runs = so.n;
+    *pos = so.pos;
+    *status = so.status;
+    return RSH_OK;
+}
+
+int rsh_debug_untokens_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t pos, int32_t T,
+                                int64_t count, uint8_t* out, int64_t span, int64_t* n_desc, int64_t* lo, int64_t* hi) {
+    if (n_desc) *n_desc = 0;
+    if (!tokens || !out || pos < 0 || !unframe_takes(T, count) || count > (tokens_len - pos) / ((int64_t)T + 4))
+        return RSH_E_INVAL;
+    std::vector<UntokSpan> spans;
+    untok_plan_run(tokens + pos, (uint32_t)T, count, out, untok_span_bytes(span), spans);
+    if (spans.size() > (size_t)INT32_MAX) return RSH_E_INVAL;
+    if (n_desc) *n_desc = (int64_t)spans.size();
+    if (ctx) {
+        RSH_CLAIM(ctx);
+        RSH_HIP(hipSetDevice(ctx->device));
+        RSH_HIP(ctx->h_untok.ensure(spans.size() * sizeof(UntokSpan)));
+        memcpy(ctx->h_untok.p, spans.data(), spans.size() * sizeof(UntokSpan));
+        uint32_t max_len = 0;
+        for (const UntokSpan& s : spans) max_len = std::max(max_len, s.len);
+        RSH_HIP(launch_token_unframe(ctx->h_untok.as<UntokSpan>(), (uint32_t)spans.size(), max_len, ctx->stream));
+        RSH_HIP(hipStreamSynchronize(ctx->stream));
+        return RSH_OK;
+    }
+    const uint8_t *l = nullptr, *u = nullptr;
+    for (const UntokSpan& s : spans) run_unspan_host(s, &l, &u);
+    if (lo) *lo = l - tokens;
+    if (hi) *hi = u - tokens;
+    return RSH_OK;
+}
 
 int rsh_receiver_combine_device(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, const rsh_header* h,
                                 const void* d_replica, int64_t replica_len, int32_t defer_write, void* d_target,

@@ -26,7 +26,8 @@
 
 #include "rsync_hip.h"
 
-#if defined(__HIPCC__)
+#if defined(RSH_HD)  // (md5_core.h's, in a source that includes both: the same meaning)
+#elif defined(__HIPCC__)
 #define RSH_HD __host__ __device__ __forceinline__
 #else
 #define RSH_HD inline

@@ -1,0 +1,207 @@
+// token_scan.h -- the Receiver's side of a token stream that lies in HBM: the token walk as runs (token_scan_kernel) and
+// the literal runs placed from the raw stream (token_unframe_kernel, the mirror of token_frame_kernel).  The run and
+// per-quantity arithmetic here is shared by the kernels (device_tokens.hip) and their host stand-ins (receiver.cpp:
+// rsh_debug_tokens_scan_selftest and rsh_debug_untokens_selftest run the same functions over host pointers).
+//
+// The walk.  A stream is tokens back to back (Receiver.java:466-525): an int v, then v bytes when v > 0; v < 0 names
+// block -(v + 1); v == 0 ends it.  The chain pos += 4 + len is dependent, but a wave proves many links per round trip:
+//   v > 0: lane i reads the int at pos + i (v + 4) when it and the v bytes after it are inside the stream; the leading
+//          lanes whose int equals v are a run of equal-length tokens (the lanes before a lane prove its position);
+//   v < 0: lane i reads the ints pos + 4 (16 i + j), j < 16; the run is the leading ints that are negative and equal
+//          v - (16 i + j): consecutive block indices.
+// A run record holds the stream offset of its first header, the kind, the token length or first block index, and the
+// token count; rounds that continue the last record extend it.  No byte outside [tokens, tokens + len) is read: headers
+// lie at any byte offset, so an int is read as its own four bytes (the compiler makes them one unaligned dword load),
+// never as an aligned quantity around it.
+//
+// Unframing.  Target byte j of a run of tokens of T bytes is stream byte (j / T)(T + 4) + 4 + j % T = j + 4 (j / T) + 4
+// from the run's first header.  A span descriptor is at most `tokens_span` target bytes of one run.  Memory rules, as
+// token_frame.h's: stores go to [dst, dst + len) only, bytewise before the first and after the last 16-byte boundary
+// of dst, one aligned 16-byte store per quantity between; loads touch only aligned 16-byte stream quantities that hold
+// at least one needed byte.  With T >= 16 at most one 4-byte header falls inside a quantity's 20 stream bytes, which
+// then lie in up to three aligned quantities; a quantity that is not needed is read as a second read of a needed one
+// (the third not at all by a wave none of whose lanes needs it).
+#pragma once
+#include "token_frame.h"
+
+namespace rsh {
+
+// ---- the walk ----
+
+struct TokRun {
+    int64_t pos;    // stream offset of the run's first header
+    int32_t kind;   // RSH_EV_LITERAL / RSH_EV_MATCH
+    int32_t v;      // LITERAL: the tokens' length; MATCH: the first block index
+    int64_t count;  // tokens
+};
+enum { TOK_SCAN_MORE = 0, TOK_SCAN_END = 1 };  // (or RSH_E_INVAL: the stream is cut short at pos)
+struct TokScanOut {
+    int64_t pos;     // END: the byte after putInt(0); MORE: the first token not listed; RSH_E_INVAL: the offending token
+    int64_t n;       // records written
+    int32_t status;
+    int32_t pad;
+};
+constexpr uint32_t kScanLanes = 64;
+// ints per lane of a match round (at 4, 2^20 consecutive match tokens took 2.78 ms to walk: kbench KBENCH_UNTOKENS,
+// DESIGN.md section 4)
+constexpr uint32_t kScanMatchPer = 16;
+
+// How many of lane `lane`'s ints continue the run that starts at pos with header v (literal: 0 or 1; match: 0 .. 16,
+// leading ones only).  ld(off): the little-endian int at stream offset off, called only with [off, off + 4) inside.
+template <class Load>
+RSH_HD uint32_t tok_scan_lane(const Load& ld, int64_t pos, int64_t len, int32_t v, uint32_t lane) {
+    if (v > 0) {
+        const int64_t off = pos + (int64_t)lane * ((int64_t)v + 4);
+        return (off + 4 + (int64_t)v <= len && ld(off) == v) ? 1u : 0u;
+    }
+    uint32_t c = 0;
+    bool run = true;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t j = 0; j < kScanMatchPer; ++j) {
+        const uint32_t idx = kScanMatchPer * lane + j;
+        const int64_t off = pos + 4 * (int64_t)idx;
+        const bool in = off + 4 <= len;
+        const int32_t x = in ? ld(off) : 0;
+        run = run && x < 0 && x == (int32_t)((uint32_t)v - idx);
+        c += run ? 1u : 0u;
+    }
+    return c;
+}
+
+// The walk from stream offset `from`: at most cap records.  head(pos): the int at pos, the same value in every lane;
+// round(pos, v): the tokens of the run that starts at pos proven in one round (>= 1: the caller of round has checked
+// the first token), the same value in every lane -- the host stand-in loops over the lanes, the kernel ballots.
+// writer: this lane stores the records and *out.
+template <class Head, class Round>
+RSH_HD void tok_scan_walk(const Head& head, const Round& round, int64_t len, int64_t from, TokRun* runs, int64_t cap,
+                          bool writer, TokScanOut* out) {
+    int64_t pos = from, n = 0;
+    int32_t status;
+    TokRun last = {0, 0, 0, 0};
+    for (;;) {
+        if (pos + 4 > len) {  // the stream ended without putInt(0)
+            status = RSH_E_INVAL;
+            break;
+        }
+        const int32_t v = head(pos);
+        if (v == 0) {
+            pos += 4;
+            status = TOK_SCAN_END;
+            break;
+        }
+        if (v > 0 && pos + 4 + (int64_t)v > len) {  // literal data past the stream's end
+            status = RSH_E_INVAL;
+            break;
+        }
+        const int32_t kind = v > 0 ? RSH_EV_LITERAL : RSH_EV_MATCH, val = v > 0 ? v : ~v;  // ~v = -(v + 1)
+        const bool ext = n > 0 && last.kind == kind && (v > 0 ? last.v == v : (int64_t)last.v + last.count == (int64_t)val);
+        if (!ext && n == cap) {
+            status = TOK_SCAN_MORE;
+            break;
+        }
+        const int64_t m = round(pos, v);
+        if (ext) {
+            last.count += m;
+        } else {
+            last = TokRun{pos, kind, val, m};
+            ++n;
+        }
+        if (writer) runs[n - 1] = last;
+        pos += v > 0 ? m * ((int64_t)v + 4) : 4 * m;
+    }
+    if (writer) *out = TokScanOut{pos, n, status, 0};
+}
+
+// ---- unframing ----
+
+struct UntokSpan {
+    const uint8_t* src;  // the stream address of the header of the span's first token (its token 0)
+    uint8_t* dst;        // where the span's first byte goes
+    int64_t L;           // the run's data bytes from token 0 on
+    uint32_t T;          // the tokens' length (>= 16)
+    uint32_t r0;         // the span's first byte as an offset in the run's data from token 0 on (< T)
+    uint32_t len;        // bytes (> 0, <= kTokMaxSpan, r0 + len <= L)
+    uint32_t pad;
+};
+
+// One output byte (the head and tail of a span), as a stream offset from token 0's header: j = r0 + the byte's offset
+// in the span.
+RSH_HD uint64_t untok_byte_off(uint32_t T, uint32_t j) { return (uint64_t)j + 4ull * (j / T) + 4; }
+
+// A 16-byte target quantity at data offset j: its first stream byte s (from token 0's header), and the bytes a (1 .. 16)
+// before the next header; a < 16: the 4 header bytes at s + a are skipped and 16 - a bytes follow them.
+struct UntokQ {
+    uint32_t s, a;
+};
+RSH_HD UntokQ untok_plan(uint32_t T, uint32_t j) {
+    const uint32_t k = j / T, left = T - (j - k * T);
+    return UntokQ{j + 4u * k + 4u, left < 16u ? left : 16u};
+}
+// The byte of the last aligned quantity needed, as an offset from the first one's address (sh = s's address & 15).
+RSH_HD uint32_t untok_extent(uint32_t sh, uint32_t a) { return sh + (a < 16u ? 19u : 15u); }
+
+// The quantity from the aligned stream quantities q0 (holding byte s at sh), q1, q2 (the next two; anything when not
+// needed): bytes below a from the 16 at s, the rest from the 16 at s + 4.  The inverse of tok_lit_merge.
+RSH_HD Q16 untok_merge(const Q16& q0, const Q16& q1, const Q16& q2, uint32_t sh, uint32_t a) {
+    const Q16 D1 = tok_funnel(q0, q1, sh);
+    const uint32_t s2 = sh + 4u;
+    const uint32_t hi = 0u - (s2 >> 4);  // s + 4 lies in q1: its 16 bytes come from q1 and q2
+    Q16 x0, x1;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 4; ++i) {
+        x0.w[i] = (q0.w[i] & ~hi) | (q1.w[i] & hi);
+        x1.w[i] = (q1.w[i] & ~hi) | (q2.w[i] & hi);
+    }
+    const Q16 D2 = tok_funnel(x0, x1, s2 & 15u);
+    Q16 r;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int w = 0; w < 4; ++w) {
+        const int d = (int)a - 4 * w;
+        const int nl = d < 0 ? 0 : d > 4 ? 4 : d;  // bytes of this dword before the header
+        const uint32_t mask = nl == 4 ? ~0u : (1u << (8 * nl)) - 1u;
+        r.w[w] = (D1.w[w] & mask) | (D2.w[w] & ~mask);
+    }
+    return r;
+}
+
+// A workgroup's part of a span, kTokBlock bytes from byte `at` on (at < len): a span of its own, re-based on the token
+// its first byte lies in -- the one division a workgroup makes beside its quantities' -- so that every offset from
+// there on fits 32 bits (r0 < T, and a quantity's stream offset is below T + 4 + (block + 16) (1 + 4 / T)).
+RSH_HD UntokSpan untok_block(UntokSpan sp, uint32_t at, uint32_t block) {
+    const uint32_t j0 = sp.r0 + at, k0 = j0 / sp.T;
+    sp.src += (uint64_t)k0 * ((uint64_t)sp.T + 4);
+    sp.L -= (int64_t)k0 * sp.T;
+    sp.r0 = j0 - k0 * sp.T;
+    sp.dst += at;
+    sp.len = sp.len - at < block ? sp.len - at : block;
+    return sp;
+}
+
+// ---- host planner ----
+
+// Appends the spans of a run of `count` tokens of T bytes whose first header is at `run`, placed at dst on:
+// ceil(count T / span) descriptors, never one per token.
+inline void untok_plan_run(const uint8_t* run, uint32_t T, int64_t count, uint8_t* dst, int64_t span,
+                           std::vector<UntokSpan>& out) {
+    const int64_t total = count * (int64_t)T;
+    for (int64_t rel = 0; rel < total; rel += span) {
+        const int64_t k0 = rel / T;
+        UntokSpan s;
+        s.src = run + k0 * ((int64_t)T + 4);
+        s.dst = dst + rel;
+        s.L = total - k0 * (int64_t)T;
+        s.T = T;
+        s.r0 = (uint32_t)(rel - k0 * (int64_t)T);
+        s.len = (uint32_t)(total - rel < span ? total - rel : span);
+        s.pad = 0;
+        out.push_back(s);
+    }
+}
+
+}  // namespace rsh

@@ -5,6 +5,8 @@
 // match integers from a descriptor alone.  The output goes through two pinned staging pieces of `tokens_piece` bytes:
 // the kernel fills one while the host copies the other into the caller's buffer, which need not be pinned.  The 20
 // trailer bytes (putInt(0), Sender.java:1316, and the file MD5, :1148) are written by the host.
+// rsh_tokens_frame_device writes the same window into device memory instead: the same spans, pointed straight at the
+// destination, in one launch without the staging.
 #include "ctx.h"
 #include "options.h"
 #include "rsync_hip_debug.h"
@@ -166,6 +168,48 @@ int write_window(rsh_ctx* c, const void* d_src, int64_t n, const rsh_event* ev, 
     return RSH_OK;
 }
 
+// One file's window into device memory (rsh_tokens_frame_device): the spans point straight at d_out, one launch, no
+// staging; the trailer's part of the window goes up from the descriptor buffer's end.
+int frame_window(rsh_ctx* c, const void* d_src, int64_t n, const rsh_event* ev, int64_t n_ev, const uint8_t md5[16],
+                 int64_t from, uint8_t* d_out, int64_t len) {
+    bool lit = false;
+    const int v = check_events(ev, n_ev, n, &lit);
+    if (v != RSH_OK) return v;
+    if (!md5 || (lit && !d_src)) return RSH_E_INVAL;
+    const int64_t size = rsh_tokens_size(ev, n_ev);
+    if (from < 0 || len < 0 || len > size - from) return RSH_E_INVAL;
+    if (len == 0) return RSH_OK;
+    if (!d_out) return RSH_E_INVAL;
+    TokWork w;
+    w.d_src = static_cast<const uint8_t*>(d_src);
+    w.ev = ev;
+    w.n_ev = n_ev;
+    w.index_events();
+    const int64_t body_end = std::min(from + len, size - kTrailer);
+    std::vector<TokSpan> spans;
+    if (body_end > from) plan_window(w, from, body_end, d_out, span_bytes(), spans);
+    if (spans.size() > (size_t)INT32_MAX) return RSH_E_INVAL;
+    const size_t desc = spans.size() * sizeof(TokSpan);
+    RSH_HIP(c->h_tokd[0].ensure(desc + 32));
+    memcpy(c->h_tokd[0].p, spans.data(), desc);
+    uint32_t max_len = 0;
+    for (const TokSpan& sp : spans) max_len = std::max(max_len, sp.len);
+    hipError_t e = launch_token_frame(c->h_tokd[0].as<TokSpan>(), (uint32_t)spans.size(), max_len, false, c->stream);
+    const int64_t a = std::max(from, size - kTrailer), b = from + len;
+    if (e == hipSuccess && b > a) {
+        uint8_t* t = c->h_tokd[0].as<uint8_t>() + desc;
+        write_trailer(md5, size, a, b - a, t);
+        e = hipMemcpyAsync(d_out + (a - from), t, (size_t)(b - a), hipMemcpyHostToDevice, c->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->stream);  // the descriptors are read until the launch is done
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        note_error(e, __LINE__, "tokens.cpp");
+        return RSH_E_DEVICE;
+    }
+    return RSH_OK;
+}
+
 // token_frame_kernel's work on one span, over host pointers: the same bytes one by one before and after the 16-byte
 // boundaries of dst, the same quantities between them from the same aligned loads.
 void run_span_host(const TokSpan& sp) {
@@ -211,6 +255,14 @@ int rsh_tokens_write_device(rsh_ctx* ctx, const void* d_src, int64_t n, const rs
     RSH_CLAIM_KEEP(ctx);
     RSH_HIP(hipSetDevice(ctx->device));
     return write_window(ctx, d_src, n, ev, n_ev, file_md5, from, out, len);
+}
+
+int rsh_tokens_frame_device(rsh_ctx* ctx, const void* d_src, int64_t n, const rsh_event* ev, int64_t n_ev,
+                            const uint8_t file_md5[16], int64_t from, void* d_out, int64_t len) {
+    if (!ctx) return RSH_E_INVAL;
+    RSH_CLAIM_KEEP(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    return frame_window(ctx, d_src, n, ev, n_ev, file_md5, from, static_cast<uint8_t*>(d_out), len);
 }
 
 int rsh_tokens_write_kept(rsh_ctx* ctx, const rsh_event* ev, int64_t n_ev, const uint8_t file_md5[16], int64_t from,

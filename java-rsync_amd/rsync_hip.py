@@ -160,6 +160,15 @@ class Md5Job(ctypes.Structure):
                 ("md5", ctypes.c_uint8 * 16)]
 
 
+class TokenRun(ctypes.Structure):
+    """rsh_token_run: one record of the token walk's run list (rsh_debug_tokens_scan_selftest)."""
+    _fields_ = [("pos", ctypes.c_int64), ("kind", ctypes.c_int32), ("value", ctypes.c_int32),
+                ("count", ctypes.c_int64)]
+
+
+COMBINE_NO_MD5 = 1
+SCAN_MORE, SCAN_END = 0, 1
+
 EVENT_DTYPE = np.dtype([("offset", "<i8"), ("length", "<i8"), ("kind", "<i4"), ("index", "<i4"),
                         ("count", "<i4"), ("reserved", "<i4")])
 
@@ -173,11 +182,12 @@ EXPORTS = ["rsh_abi_version", "rsh_strerror", "rsh_last_error", "rsh_device_coun
            "rsh_tokens_write_device", "rsh_tokens_write_kept", "rsh_tokens_write_batch_device",
            "rsh_sums_wire_size", "rsh_header_from_wire", "rsh_sums_frame_device", "rsh_sums_unframe_device",
            "rsh_block_sums_batch_wire", "rsh_match_scan_batch_wire", "rsh_block_sums_batch_wire_multi",
-           "rsh_match_scan_batch_wire_multi"]
+           "rsh_match_scan_batch_wire_multi", "rsh_tokens_frame_device", "rsh_receiver_combine_resident"]
 # include/rsync_hip_debug.h (testing / diagnostics ABI)
 DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_reset_options", "rsh_debug_k1_clock",
                  "rsh_debug_streams_busy", "rsh_debug_kernel_ms", "rsh_debug_multi_selftest", "rsh_debug_generation",
-                 "rsh_debug_tokens_selftest", "rsh_debug_sums_selftest"]
+                 "rsh_debug_tokens_selftest", "rsh_debug_sums_selftest", "rsh_debug_tokens_scan_selftest",
+                 "rsh_debug_untokens_selftest"]
 
 _LIB = None
 
@@ -294,6 +304,13 @@ def lib():
         "rsh_match_scan_batch_wire_multi": ([ctypes.POINTER(P), I32, ctypes.POINTER(SendJob), I32, P,
                                              ctypes.POINTER(ScanStats)], ctypes.c_int),
         "rsh_debug_sums_selftest": ([I32, HP, P, P, P, I64, I64, ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_tokens_frame_device": ([P, P, I64, P, I64, P, I64, P, I64], ctypes.c_int),
+        "rsh_receiver_combine_resident": ([P, P, I64, HP, P, I64, I32, P, I64, I32, ctypes.POINTER(CombineResult)],
+                                          ctypes.c_int),
+        "rsh_debug_tokens_scan_selftest": ([P, P, I64, I64, ctypes.POINTER(TokenRun), I64, ctypes.POINTER(I64),
+                                            ctypes.POINTER(I64), ctypes.POINTER(I32)], ctypes.c_int),
+        "rsh_debug_untokens_selftest": ([P, P, I64, I64, I32, I64, P, I64, ctypes.POINTER(I64), ctypes.POINTER(I64),
+                                         ctypes.POINTER(I64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -438,6 +455,38 @@ def tokens_selftest(src, ev, file_md5_bytes, start=0, length=None, span=0, out=N
     _check(lib().rsh_debug_tokens_selftest(_ptr(a) if a.size else None, a.size, _ptr(ev) if ev.size else None, ev.size,
                                            _ptr(fm), start, _ptr(out), length, span, ctypes.byref(nd)))
     return out[:max(length, 0)].tobytes(), nd.value
+
+
+def _addr(x):
+    """A host array's or DeviceBuffer's address, or a plain address, as c_void_p."""
+    if isinstance(x, np.ndarray):
+        return ctypes.c_void_p(x.ctypes.data)
+    if isinstance(x, DeviceBuffer):
+        return x.ptr
+    return ctypes.c_void_p(x or None)
+
+
+def tokens_scan_selftest(tokens, length, start=0, cap=1 << 16, ctx=None):
+    """rsh_debug_tokens_scan_selftest: one pass of the token walk from stream offset `start` with room for cap run
+    records: ([(pos, kind, value, count)], end position, status SCAN_END / SCAN_MORE / RSH_E_INVAL).  ctx None: tokens
+    is a uint8 array (any alignment) walked by the host stand-in; with a Context, tokens is a DeviceBuffer or a device
+    address and token_scan_kernel runs."""
+    runs = (TokenRun * cap)()
+    n, pos, st = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+    _check(lib().rsh_debug_tokens_scan_selftest(None if ctx is None else ctx.handle, _addr(tokens), length, start, runs,
+                                                cap, ctypes.byref(n), ctypes.byref(pos), ctypes.byref(st)))
+    return [(r.pos, r.kind, r.value, r.count) for r in runs[:n.value]], pos.value, st.value
+
+
+def untokens_selftest(tokens, length, pos, T, count, out, span=0, ctx=None):
+    """rsh_debug_untokens_selftest: the literal run of `count` tokens of T bytes at stream offset pos placed at `out`
+    in spans of `span` bytes: (descriptor count, lowest stream offset loaded, one past the highest).  ctx None: uint8
+    arrays and the host stand-in of token_unframe_kernel; with a Context: device addresses and the kernel (the load
+    extent is then not reported)."""
+    nd, lo, hi = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().rsh_debug_untokens_selftest(None if ctx is None else ctx.handle, _addr(tokens), length, pos, T, count,
+                                             _addr(out), span, ctypes.byref(nd), ctypes.byref(lo), ctypes.byref(hi)))
+    return nd.value, lo.value, hi.value
 
 
 def sums_wire_size(h):
@@ -780,6 +829,28 @@ class Context:
         return self._tokens_window(
             lambda e, ne, fm, a, o, ln: lib().rsh_tokens_write_device(self._p, ptr, n, e, ne, fm, a, o, ln),
             ev, md5, start, length)
+
+    def tokens_frame_device(self, d_src, n, ev, md5, d_out, start=0, length=None):
+        """rsh_tokens_frame_device: as tokens_device, written into device memory at d_out (a DeviceBuffer or a device
+        address, any alignment) instead of a host buffer.  Returns the byte count written."""
+        ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+        fm = np.frombuffer(bytes(md5), np.uint8).copy()
+        if length is None:
+            length = tokens_size(ev) - start
+        _check(lib().rsh_tokens_frame_device(self._p, _addr(d_src), n, _ptr(ev) if ev.size else None, ev.size,
+                                             _ptr(fm), start, _addr(d_out), length))
+        return length
+
+    def receiver_combine_resident(self, d_tokens, tokens_len, h, d_replica, replica_len, d_target, target_cap,
+                                  defer_write=False, flags=0):
+        """rsh_receiver_combine_resident: Receiver.combineDataToFile with the token stream, the replica (None: no
+        replica) and the target all in HBM (DeviceBuffers or device addresses): (status, CombineResult).  The status
+        is returned, not raised."""
+        r = CombineResult()
+        rc = lib().rsh_receiver_combine_resident(self._p, _addr(d_tokens), tokens_len, ctypes.byref(h),
+                                                 _addr(d_replica), replica_len, int(bool(defer_write)),
+                                                 _addr(d_target), target_cap, flags, ctypes.byref(r))
+        return rc, r
 
     def tokens_kept(self, ev, md5, start=0, length=None):
         """rsh_tokens_write_kept: as tokens_device over the source this context's last single-file scan left in HBM;

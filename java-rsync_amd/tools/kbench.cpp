@@ -20,8 +20,9 @@
 
 #include "device.h"
 #include "token_frame.h"
+#include "token_scan.h"
 
-#define CK(x)                                                                   \
+#define CK(x)                                                                  \
     do {                                                                        \
         hipError_t e = (x);                                                     \
         if (e != hipSuccess) {                                                  \
@@ -156,7 +157,143 @@ static int tokens_main(int argc, char** argv) {
     return same ? 0 : 1;
 }
 
+// KBENCH_UNTOKENS=<span bytes>: the Receiver's side of a stream in HBM (device_tokens.hip).  The stream is the first
+// <MiB> of one all-literal event's stream (8192-byte tokens), framed on the device and closed with putInt(0).
+//   * token_unframe_kernel placing its literal bytes (HBM to HBM, spans of that many bytes; 0: 256 KiB) against the
+//     production gather copying the same number of bytes in 1 MiB ops, alternating rep by rep;
+//   * token_scan_kernel walking it, and walking a stream of 2^20 consecutive match tokens, each against a
+//     device-to-host copy of the same stream (the download a host walk needs), into pageable and into pinned memory.
+static int untokens_main(int argc, char** argv) {
+    const int64_t count = ((int64_t)atoll(argv[1]) << 20) / rsh::kTokStride;  // whole tokens
+    const int64_t n = count * rsh::kTokData, slen = count * rsh::kTokStride + 4;
+    int64_t span = atoll(getenv("KBENCH_UNTOKENS"));
+    if (span <= 0) span = 256 << 10;
+    const int reps = atoi(argv[4]);
+    hipStream_t s;
+    CK(hipStreamCreate(&s));
+    uint8_t *src, *stream, *dst;
+    CK(hipMalloc(&src, n));
+    CK(hipMalloc(&stream, slen));
+    CK(hipMalloc(&dst, n));
+    CK(rsh::launch_fill_splitmix(src, n, 0x5EED, 0, s));
+    CK(hipMemsetAsync(stream + slen - 4, 0, 4, s));
+    {
+        const rsh_event e{0, n, RSH_EV_LITERAL, 0, 0, 0};
+        std::vector<rsh::TokSpan> fs;
+        rsh::tok_plan_event(e, src, 0, slen - 4, stream, 256 << 10, fs);
+        rsh::TokSpan* d_fs;
+        CK(hipMalloc(&d_fs, fs.size() * sizeof(rsh::TokSpan)));
+        CK(hipMemcpy(d_fs, fs.data(), fs.size() * sizeof(rsh::TokSpan), hipMemcpyHostToDevice));
+        CK(rsh::launch_token_frame(d_fs, (uint32_t)fs.size(), 256 << 10, false, s));
+        CK(hipStreamSynchronize(s));
+    }
+    std::vector<rsh::UntokSpan> spans;
+    rsh::untok_plan_run(stream, rsh::kTokData, count, dst, span, spans);
+    rsh::UntokSpan* d_spans;
+    CK(hipMalloc(&d_spans, spans.size() * sizeof(rsh::UntokSpan)));
+    CK(hipMemcpy(d_spans, spans.data(), spans.size() * sizeof(rsh::UntokSpan), hipMemcpyHostToDevice));
+    const int64_t op = 1 << 20;
+    std::vector<rsh::GatherOp> ops;
+    for (int64_t o = 0; o < n; o += op) ops.push_back(rsh::GatherOp{src + o, dst + o, std::min(op, n - o)});
+    rsh::GatherOp* d_ops;
+    CK(hipMalloc(&d_ops, ops.size() * sizeof(rsh::GatherOp)));
+    CK(hipMemcpy(d_ops, ops.data(), ops.size() * sizeof(rsh::GatherOp), hipMemcpyHostToDevice));
+    // parity: three 20 KiB ranges of the unframed target against the source the stream was framed from
+    CK(hipMemset(dst, 0, n));
+    CK(rsh::launch_token_unframe(d_spans, (uint32_t)spans.size(), (uint32_t)std::min(span, n), s));
+    CK(hipStreamSynchronize(s));
+    bool same = true;
+    const int64_t chk = std::min<int64_t>(20 << 10, n);
+    std::vector<uint8_t> a((size_t)chk), b((size_t)chk);
+    for (int64_t q : {(int64_t)0, n / 3, n - chk}) {
+        CK(hipMemcpy(a.data(), src + q, (size_t)chk, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(b.data(), dst + q, (size_t)chk, hipMemcpyDeviceToHost));
+        same = same && a == b;
+    }
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    float best[2] = {1e30f, 1e30f}, tot[2] = {0, 0};
+    for (int r = 0; r < reps + 1; ++r) {  // (the first round warms both up)
+        for (int w = 0; w < 2; ++w) {
+            CK(hipEventRecord(e0, s));
+            if (w == 0) CK(rsh::launch_token_unframe(d_spans, (uint32_t)spans.size(), (uint32_t)std::min(span, n), s));
+            else CK(rsh::launch_gather_ops_variant(6, d_ops, (uint32_t)ops.size(), s));
+            CK(hipEventRecord(e1, s));
+            CK(hipEventSynchronize(e1));
+            float ms;
+            CK(hipEventElapsedTime(&ms, e0, e1));
+            if (r == 0) continue;
+            best[w] = ms < best[w] ? ms : best[w];
+            tot[w] += ms;
+        }
+    }
+    const char* name[2] = {"token_unframe", "gather <1024,4,nt,nt>"};
+    for (int w = 0; w < 2; ++w)
+        printf("%-22s n=%lld %s=%lld descriptors=%zu  avg %.3f ms  best %.3f ms  %.1f GB/s (read+write; %.3f of 8 TB/s)%s\n",
+               name[w], (long long)n, w ? "op" : "span", (long long)(w ? op : span), w ? ops.size() : spans.size(),
+               tot[w] / reps, best[w], 2.0 * n / (tot[w] / reps / 1e3) / 1e9, 2.0 * n / (tot[w] / reps / 1e3) / 8e12,
+               w ? "" : (same ? "  unframe=ok" : "  unframe=MISMATCH"));
+    printf("token_unframe / gather: avg %.3f  best %.3f\n", tot[0] / tot[1], best[0] / best[1]);
+    // the walk against the download of the same stream
+    const int64_t nmatch = 1 << 20, mlen = 4 * nmatch + 4;
+    uint8_t* mstream;
+    CK(hipMalloc(&mstream, mlen));
+    CK(hipMemset(mstream + mlen - 4, 0, 4));
+    {
+        const rsh_event e{0, 0, RSH_EV_MATCH, 5, (int32_t)nmatch, 0};
+        std::vector<rsh::TokSpan> fs;
+        rsh::tok_plan_event(e, nullptr, 0, mlen - 4, mstream, 256 << 10, fs);
+        rsh::TokSpan* d_fs;
+        CK(hipMalloc(&d_fs, fs.size() * sizeof(rsh::TokSpan)));
+        CK(hipMemcpy(d_fs, fs.data(), fs.size() * sizeof(rsh::TokSpan), hipMemcpyHostToDevice));
+        CK(rsh::launch_token_frame(d_fs, (uint32_t)fs.size(), 256 << 10, false, s));
+        CK(hipStreamSynchronize(s));
+    }
+    rsh::TokRun* d_runs;
+    rsh::TokScanOut* d_out;
+    CK(hipMalloc(&d_runs, 1024 * sizeof(rsh::TokRun)));
+    CK(hipMalloc(&d_out, sizeof(rsh::TokScanOut)));
+    uint8_t* pinned;
+    CK(hipHostMalloc(&pinned, (size_t)std::max(slen, mlen), hipHostMallocDefault));
+    std::vector<uint8_t> pageable((size_t)std::max(slen, mlen));
+    bool walk_ok = true;
+    for (int w = 0; w < 2; ++w) {
+        const uint8_t* st = w ? mstream : stream;
+        const int64_t len = w ? mlen : slen;
+        float t[3] = {0, 0, 0}, bt[3] = {1e30f, 1e30f, 1e30f};
+        for (int r = 0; r < reps + 1; ++r) {
+            for (int k = 0; k < 3; ++k) {
+                CK(hipStreamSynchronize(s));
+                CK(hipEventRecord(e0, s));
+                if (k == 0) CK(rsh::launch_token_scan(st, len, 0, d_runs, 1024, d_out, s));
+                else CK(hipMemcpyAsync(k == 1 ? pageable.data() : pinned, st, (size_t)len, hipMemcpyDeviceToHost, s));
+                CK(hipEventRecord(e1, s));
+                CK(hipEventSynchronize(e1));
+                float ms;
+                CK(hipEventElapsedTime(&ms, e0, e1));
+                if (r == 0) continue;
+                t[k] += ms;
+                bt[k] = ms < bt[k] ? ms : bt[k];
+            }
+        }
+        rsh::TokScanOut so;
+        rsh::TokRun run;
+        CK(hipMemcpy(&so, d_out, sizeof(so), hipMemcpyDeviceToHost));
+        CK(hipMemcpy(&run, d_runs, sizeof(run), hipMemcpyDeviceToHost));
+        const bool ok = so.status == rsh::TOK_SCAN_END && so.pos == len && so.n == 1 &&
+                        run.count == (w ? nmatch : count) && run.v == (w ? 5 : (int32_t)rsh::kTokData);
+        walk_ok = walk_ok && ok;
+        printf("token_scan %-8s stream=%lld bytes  walk avg %.3f ms best %.3f ms (%.3f ms per GiB)  d2h pageable avg %.3f ms  "
+               "d2h pinned avg %.3f ms  walk / d2h pinned %.3f  runs=%lld %s\n",
+               w ? "matches" : "literals", (long long)len, t[0] / reps, bt[0], t[0] / reps * (double)(1 << 30) / (double)len,
+               t[1] / reps, t[2] / reps, t[0] / t[2], (long long)so.n, ok ? "walk=ok" : "walk=MISMATCH");
+    }
+    return same && walk_ok ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 5 && getenv("KBENCH_UNTOKENS")) return untokens_main(argc, argv);
     if (argc >= 6 && getenv("KBENCH_GATHER")) return gather_main(argc, argv);
     if (argc >= 5 && getenv("KBENCH_TOKENS")) return tokens_main(argc, argv);
     if (argc < 6) {
