@@ -7,7 +7,10 @@
  * Tests force rare paths with them; a few are tunables: k1_gather, k1_shift,
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
- * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs.
+ * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma.
+ *
+ * k1_dma = 1 (default): the main waves of the pipelined K1 stream their stages from HBM straight into LDS wherever
+ * every wave's base is 16-B aligned; 0: the register-staged form at every base (the A/B partner, from one library).
  *
  * fault_inject is a bit set: bit 0 (1) fails a segment or Receiver pass's HBM allocation (RSH_E_NOMEM), bit 1 (2) a
  * segment pass's copies (RSH_E_DEVICE); bit 2 (4) limits both to member 1 of a multi-context call; bit 3 (8) limits
@@ -53,6 +56,12 @@ int rsh_debug_streams_busy(rsh_ctx* ctx, int32_t* mask);
  * reports it beside the headline (k1_clock_ghz). */
 int rsh_debug_k1_clock(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t block_length, int32_t reps,
                        double* clock_ghz);
+
+/* The swizzle of the pipelined K1's DMA-form LDS image (a stage: 64 chunks x eight 16-B pieces, slot p of chunk c at
+ * byte 128 c + 16 p), without a device.  what = 0: the piece that the lane filling slot `index` of `chunk` fetches;
+ * 1: the slot from which reader lane `chunk` takes piece `index`; 2: the LDS byte address of slot `index` of `chunk`.
+ * -1 for arguments outside chunk 0..63, index 0..7, what 0..2. */
+int32_t rsh_debug_k1_dma_swizzle(int32_t what, int32_t chunk, int32_t index);
 
 /* The multi-context segment driver (rsh_*_batch_multi: split, one member call per part, merge) with a stand-in member
  * call and no device: part p's call records per job its part (part_out) and its position among the part's files

@@ -540,6 +540,12 @@ void rsh_debug_reset_options(void) {
     for (int i = 0; i < rsh::OPT_COUNT; ++i) rsh::opt_table()[i].store(rsh::opt_info()[i].def, std::memory_order_relaxed);
 }
 
+int32_t rsh_debug_k1_dma_swizzle(int32_t what, int32_t chunk, int32_t index) {
+    if (what < 0 || what > 2 || chunk < 0 || chunk > 63 || index < 0 || index > 7) return -1;
+    const uint32_t c = (uint32_t)chunk, i = (uint32_t)index;
+    return (int32_t)(what == 0 ? rsh::k1_dma_piece(c, i) : what == 1 ? rsh::k1_dma_slot(c, i) : rsh::k1_dma_lds_byte(c, i));
+}
+
 int rsh_debug_kernel_ms(rsh_ctx* ctx, int32_t which, double* ms) {
     if (!ctx || !ms || which < 0 || which > 2) return RSH_E_INVAL;
     *ms = -1.0;

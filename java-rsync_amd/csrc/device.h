@@ -107,6 +107,15 @@ uint32_t plan_block_sums_files(const K1File* files, int32_t nfiles, std::vector<
 hipError_t launch_expand_groups(const K1Plan* d_plans, uint32_t nplans, uint32_t ngroups, K1Group* d_groups,
                                 hipStream_t s);
 bool tail_gather_on();  // option k1_gather = 0: leftover chunks one per lane, no gathered waves
+// The LDS image of the pipelined K1's DMA form (option k1_dma; block_sums_pipe_body<.., DMA>): a stage is the next
+// 128 B of a wave's 64 chunks, 8 KiB with no pad -- the 16-B slot p of chunk c at byte 128 c + 16 p.  The lane that
+// fills (chunk c, slot p) fetches the chunk's piece k1_dma_piece(c, p); reader lane c takes piece k from slot
+// k1_dma_slot(c, k).  The XOR with (c >> 1) & 7 spreads the 16 lanes of a ds_read_b128 group over all 64 banks.
+constexpr uint32_t K1_DMA_STAGE = 8192;
+constexpr uint32_t k1_dma_piece(uint32_t c, uint32_t p) { return p ^ ((c >> 1) & 7u); }
+constexpr uint32_t k1_dma_slot(uint32_t c, uint32_t k) { return k ^ ((c >> 1) & 7u); }
+constexpr uint32_t k1_dma_lds_byte(uint32_t c, uint32_t slot) { return 128u * c + 16u * slot; }
+bool k1_dma_on();  // option k1_dma = 0: the register-staged form at every base
 // partial: some groups have count < 64 (plan_block_sums_files) -- they run as gathered waves of the same launch
 hipError_t launch_block_sums_batch(const K1Group* d_groups, uint32_t ngroups, const K1Lane* d_lanes, uint32_t nlanes,
                                    int lane_align, uint32_t seed_word, hipStream_t s, const int* abort_flag = nullptr,

@@ -304,7 +304,12 @@ __device__ __forceinline__ void md5_stream_block(Md5State& st, const uint32_t (&
 // ABORT: the wave polls *abort_flag (never_word() when the launch has no abort word of its own).
 // WEAKV (kbench A/B only, variant 1010): the weak sums on the VALU (weak_block: 32 v_dot4_i32_i8 per 64-B block)
 // instead of the matrix pipe -- the form that drops the MFMAs' power for 8 % more VALU issue.
-template <bool MULTI = false, bool GATHER = false, bool WEAKV = false>
+// DMA (the main waves at 16-B aligned bases, option k1_dma): the stages go from HBM straight into LDS, below.
+// DIAG (kbench only, the DMA form's diagnostic builds; their sums are not the chunks'): 1 = compute only -- the
+// descriptor has zero records, so the range check drops every load while the instruction stream and the waits stay
+// (variant 1023); 2 = loads only -- the stage's words are folded with one XOR per 16 bytes instead of MD5 and the
+// MFMAs (variant 1024).
+template <bool MULTI = false, bool GATHER = false, bool WEAKV = false, bool DMA = false, int DIAG = 0>
 __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__ data, uint32_t B, uint32_t dl,
                                                              uint32_t seed, int32_t* __restrict__ weak_out,
                                                              uint8_t* __restrict__ strong_out,
@@ -381,8 +386,161 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
             }
     }
 
-    uint4 q[2][8];  // load slots: stage s+1 and s+2 in flight while stage s computes
+    Md5State st = md5_init();
+    auto md5_block = [&](const uint4 (&w)[4]) __attribute__((always_inline)) {
+        if constexpr (DIAG == 2) {  // loads only: every word read from LDS is used, nothing else runs
+#pragma unroll
+            for (int k = 0; k < 4; ++k) st.a ^= w[k].x ^ w[k].y ^ w[k].z ^ w[k].w;
+            return;
+        }
+        uint32_t m[16];
+        unpack(w, m);
+        md5_stream_block(st, m);
+    };
+    [[maybe_unused]] int32_t vs1 = 0, vu = 0;  // WEAKV: the lane's own sums
+    auto weak_words = [&](const uint4 (&w)[4], [[maybe_unused]] uint32_t off) __attribute__((always_inline)) {
+        if constexpr (DIAG == 2) return;
+        if constexpr (WEAKV) {  // one 64-B block at chunk offset off
+            uint32_t m[16];
+            unpack(w, m);
+            weak_block(m, vs1, vu, off);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) RW[e] += accW[e];  // R += P_{b-1}
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const v4i32 b4 = {(int)w[k].x, (int)w[k].y, (int)w[k].z, (int)w[k].w};
+                accW = __builtin_amdgcn_mfma_i32_16x16x64_i8(wW[k], b4, accW, 0, 0, 0);
+            }
+        }
+    };
     uint4 Wa[4];    // words of the current stage's block 0 (then: the next stage's block 0)
+    if constexpr (DMA) {
+        // DMA (option k1_dma, the default at 16-B aligned bases): the stage goes from HBM straight into LDS
+        // (buffer_load_dwordx4 ... lds): no staging VGPRs, no ds_write_b128.  One instruction writes 1 KiB lane-linear
+        // (M0 + 16 l), so the image has no pad slot: a stage is 8 KiB, chunk c's 16-B slot p at 128 c + 16 p, row j
+        // = chunks 8 j + (l >> 3).  Bank conflicts of the readers are taken out by a swizzle on the SOURCE address:
+        // the lane that fills slot p of chunk c fetches piece p ^ ((c >> 1) & 7) (k1_dma_piece), reader lane c takes
+        // piece k from slot k ^ ((c >> 1) & 7): 16 consecutive lanes of a ds_read_b128 then cover all 64 banks.
+        // Schedule, two 8 KiB slots per wave: at the top of stage s the words of stage s are in registers (read
+        // between the blocks of stage s - 1), so slot s & 1 is free once those reads have retired (lgkmcnt(0), no
+        // stall: they were issued half a stage ago) and takes stage s + 2; stage s + 1 is read between the two
+        // blocks of stage s behind s_waitcnt vmcnt(8) -- only stage s + 2's eight loads may still be in flight --
+        // so a load has 1.5 stages between issue and first read.  The wave is the workgroup: its own vmcnt orders
+        // the ds_reads, no barrier.  hipcc drains vmcnt(0) at any ds_read behind an LDS load it knows of, so the
+        // loads and their waits are inline assembly (M0 saved, set and restored inside the statement).  Every exit
+        // waits vmcnt(0): a retired wave's LDS goes to the next workgroup, a late load would land in it.
+        static_assert(!GATHER && !WEAKV, "the DMA form is the main waves' form only");
+        B = (uint32_t)__builtin_amdgcn_readfirstlane((int)B);
+        const uint64_t ga = reinterpret_cast<uint64_t>(gdata);
+        const v4i32 desc = {__builtin_amdgcn_readfirstlane((int)(uint32_t)ga),
+                            __builtin_amdgcn_readfirstlane((int)((uint32_t)(ga >> 32) & 0xFFFFu)),
+                            DIAG == 1 ? 0 : (int)(64u * B),
+                            0x00020000};  // as make_buffer_rsrc(gdata, 0, 64 B, 0x00020000)
+        const uint32_t lds0 = __builtin_amdgcn_readfirstlane(
+            (int)(uint32_t)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) void*)lds_all));
+        // rows 8 j of even j fetch piece (l & 7) ^ (l >> 4), of odd j that ^ 4: the lane offset's bit 6
+        const uint32_t voff = (uint32_t)(l >> 3) * B + 16u * k1_dma_piece((uint32_t)(l >> 3), (uint32_t)(l & 7));
+        const uint32_t so1 = 8u * B, so2 = 16u * B, so3 = 24u * B, so4 = 32u * B, so5 = 40u * B, so6 = 48u * B,
+                       so7 = 56u * B;
+        auto dma = [&](int slot, uint32_t stg) __attribute__((always_inline)) {
+            uint32_t keep;
+            const uint32_t ve = voff + 128u * stg, vo = ve ^ 64u;
+            asm volatile(
+                "s_nop 4\n\t"
+                "s_waitcnt lgkmcnt(0)\n\t"
+                "s_mov_b32 %0, m0\n\t"
+                "s_mov_b32 m0, %4\n\t"
+                "s_nop 0\n\t"
+                "buffer_load_dwordx4 %2, %1, 0 offen nt lds\n\t"
+                "s_add_u32 m0, m0, 0x400\n\t"
+                "s_nop 0\n\t"
+                "buffer_load_dwordx4 %3, %1, %5 offen nt lds\n\t"
+                "s_add_u32 m0, m0, 0x400\n\t"
+                "s_nop 0\n\t"
+                "buffer_load_dwordx4 %2, %1, %6 offen nt lds\n\t"
+                "s_add_u32 m0, m0, 0x400\n\t"
+                "s_nop 0\n\t"
+                "buffer_load_dwordx4 %3, %1, %7 offen nt lds\n\t"
+                "s_add_u32 m0, m0, 0x400\n\t"
+                "s_nop 0\n\t"
+                "buffer_load_dwordx4 %2, %1, %8 offen nt lds\n\t"
+                "s_add_u32 m0, m0, 0x400\n\t"
+                "s_nop 0\n\t"
+                "buffer_load_dwordx4 %3, %1, %9 offen nt lds\n\t"
+                "s_add_u32 m0, m0, 0x400\n\t"
+                "s_nop 0\n\t"
+                "buffer_load_dwordx4 %2, %1, %10 offen nt lds\n\t"
+                "s_add_u32 m0, m0, 0x400\n\t"
+                "s_nop 0\n\t"
+                "buffer_load_dwordx4 %3, %1, %11 offen nt lds\n\t"
+                "s_mov_b32 m0, %0"
+                : "=&s"(keep)
+                : "s"(desc), "v"(ve), "v"(vo), "s"(lds0 + (uint32_t)slot * K1_DMA_STAGE), "s"(so1), "s"(so2), "s"(so3),
+                  "s"(so4), "s"(so5), "s"(so6), "s"(so7)
+                : "memory", "scc");
+        };
+        const uint32_t rdx = ((uint32_t)l >> 1) & 7u;
+        auto get_stage = [&](uint4 (&w0)[4], uint4 (&w1)[4], int slot) __attribute__((always_inline)) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w0[k] = lds_all[slot * 512 + 8 * l + (int)((uint32_t)k ^ rdx)];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w1[k] = lds_all[slot * 512 + 8 * l + (int)((uint32_t)(4 + k) ^ rdx)];
+        };
+        uint4 Wb[2][4];  // block-1 words of the stage of either parity
+        int flag = 0;
+        // One stage with compile-time parity P: slot P held it; its words are in Wa and Wb[P].
+        auto stage = [&](auto pc, uint32_t si, bool has_next, bool refill, bool poll) __attribute__((always_inline)) {
+            constexpr int P = decltype(pc)::value;
+            if (refill) dma(P, si + 2);
+            // the abort word's load after the statement above (it waits lgkmcnt(0)), compared two stages later
+            if (poll) asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(flag) : "s"(abort_flag));
+            md5_block(Wa);
+            weak_words(Wa, 128u * si);
+            compiler_fence();
+            if (has_next) {
+                // "+v"(st.a): the MD5 statements are neither volatile nor memory operations, so only the digest state
+                // keeps the wait (and the reads below it) between the two blocks instead of early in block 0
+                if (refill) asm volatile("s_waitcnt vmcnt(8)" : "+v"(st.a) : : "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" : "+v"(st.a) : : "memory");
+                get_stage(Wa, Wb[P ^ 1], P ^ 1);
+                // all eight reads here, none sunk to the end of block 1 where the next refill's lgkmcnt(0) would stall
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            md5_block(Wb[P]);
+            weak_words(Wb[P], 128u * si + 64u);
+            compiler_fence();
+        };
+        dma(0, 0);
+        dma(1, 1);
+        if constexpr (MULTI) {  // a group whose file was resolved before the wave started does nothing
+            int f0;
+            asm volatile("s_load_dword %0, %1, 0x0 glc\n\ts_waitcnt lgkmcnt(0)" : "=s"(f0) : "s"(abort_flag));
+            if (f0 == abort_gen) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                return;
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        get_stage(Wa, Wb[0], 0);
+        uint32_t s = 0;
+        // steady state, branch-free: exactly two stages of loads in flight below each refill
+        for (; s + 5 <= nst && flag != abort_gen; s += 2) {
+            stage(std::integral_constant<int, 0>{}, s, true, true, true);
+            stage(std::integral_constant<int, 1>{}, s + 1, true, true, false);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(flag));
+        }
+        if (flag == abort_gen) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            return;
+        }
+        for (; s < nst; s += 2) {  // drain
+            stage(std::integral_constant<int, 0>{}, s, s + 1 < nst, s + 2 < nst, false);
+            if (s + 1 < nst) stage(std::integral_constant<int, 1>{}, s + 1, s + 2 < nst, s + 3 < nst, false);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+    uint4 q[2][8];  // load slots: stage s+1 and s+2 in flight while stage s computes
     uint4 Wb[4];    // words of the current stage's block 1
     // Buffer loads: the wave's 64 chunks (64 * B <= 8 MiB) behind one descriptor, a 32-bit lane offset and
     // a scalar offset per 8-chunk row j -- one VGPR of addressing instead of eight 64-bit pointers.
@@ -407,28 +565,6 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
     auto get_words = [&](uint4 (&w)[4], int buf, int h) __attribute__((always_inline)) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) w[k] = lds_all[buf * BUF + rd0 + 4 * h + k];
-    };
-    Md5State st = md5_init();
-    auto md5_block = [&](const uint4 (&w)[4]) __attribute__((always_inline)) {
-        uint32_t m[16];
-        unpack(w, m);
-        md5_stream_block(st, m);
-    };
-    [[maybe_unused]] int32_t vs1 = 0, vu = 0;  // WEAKV: the lane's own sums
-    auto weak_words = [&](const uint4 (&w)[4], [[maybe_unused]] uint32_t off) __attribute__((always_inline)) {
-        if constexpr (WEAKV) {  // one 64-B block at chunk offset off
-            uint32_t m[16];
-            unpack(w, m);
-            weak_block(m, vs1, vu, off);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) RW[e] += accW[e];  // R += P_{b-1}
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const v4i32 b4 = {(int)w[k].x, (int)w[k].y, (int)w[k].z, (int)w[k].w};
-                accW = __builtin_amdgcn_mfma_i32_16x16x64_i8(wW[k], b4, accW, 0, 0, 0);
-            }
-        }
     };
     // One stage with compile-time parity P: LDS buffer P holds it, q[P ^ 1] the next stage's data.
     // Block-1 words are read at the top (they land during block 0); the next stage's block-0 words are read
@@ -478,6 +614,7 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
         stage(std::integral_constant<int, 0>{}, s, s + 1 < nst, s + 3 < nst);
         if (s + 1 < nst) stage(std::integral_constant<int, 1>{}, s + 1, s + 2 < nst, s + 4 < nst);
     }
+    }  // !DMA
     {
         const uint64_t bits = ((uint64_t)B + 4) * 8;
         uint32_t m[16] = {seed, 0x80u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, (uint32_t)bits, (uint32_t)(bits >> 32)};
@@ -519,6 +656,26 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
     store_digest(strong_out + (size_t)c * dl, st, dl);
 }
 
+// the swizzle of the DMA form's image: every 16-lane ds_read_b128 group of every piece k covers the 64 banks once
+// (16 distinct 4-bank spans), and a reader's slot of piece k holds piece k
+constexpr bool k1_dma_swizzle_ok() {
+    for (uint32_t k = 0; k < 8; ++k)
+        for (uint32_t g = 0; g < 4; ++g) {
+            uint32_t spans = 0;
+            for (uint32_t i = 0; i < 16; ++i) {
+                const uint32_t c = 16 * g + i, slot = k1_dma_slot(c, k);
+                if (slot > 7 || k1_dma_piece(c, slot) != k) return false;
+                spans |= 1u << ((k1_dma_lds_byte(c, slot) >> 4) & 15u);
+            }
+            if (spans != 0xFFFFu) return false;
+        }
+    return true;
+}
+static_assert(k1_dma_swizzle_ok(), "K1 DMA image: bank conflict or slot / piece mismatch");
+bool k1_dma_on() { return opt(OPT_K1_DMA) != 0; }
+
+// block_sums_pipe_kernel: the main waves in the DMA form (16-B aligned bases, option k1_dma);
+// block_sums_pipe_reg_kernel: the register-staged form (any base, k1_dma = 0).
 template <bool MULTI = false>
 __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_kernel(const uint8_t* __restrict__ data, uint32_t B, uint32_t dl,
                                                              uint32_t seed, int32_t* __restrict__ weak_out,
@@ -527,6 +684,15 @@ __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_kernel(const 
                                                              const K1Group* __restrict__ groups = nullptr,
                                                              int64_t n = 0, uint32_t nchunks = 0,
                                                              uint32_t main_waves = 0xFFFFFFFFu) {
+    block_sums_pipe_body<MULTI, false, false, true>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen,
+                                                    groups, n, nchunks, main_waves);
+}
+template <bool MULTI = false>
+__global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_reg_kernel(
+    const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
+    uint8_t* __restrict__ strong_out, const int* abort_flag = nullptr, int abort_gen = 0,
+    const K1Group* __restrict__ groups = nullptr, int64_t n = 0, uint32_t nchunks = 0,
+    uint32_t main_waves = 0xFFFFFFFFu) {
     block_sums_pipe_body<MULTI>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen, groups, n, nchunks,
                                 main_waves);
 }
@@ -535,7 +701,9 @@ __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_kernel(const 
 // per-lane wave runs ~20% slower than a coalesced one and, when every wave runs in the first round, sets the
 // launch's end.  Used only for launches with such a tail: the exact-multiple launches keep
 // block_sums_pipe_kernel.  Its register budget is 256 (2 waves/SIMD): under K1_PIPE_ATTR the two bodies spill.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void block_sums_pipe_tailg_kernel(
+// DMA: the main waves' form (block_sums_pipe_tailg_kernel; the register-staged one is ..._tailg_reg_kernel).
+template <bool DMA>
+__device__ __forceinline__ void block_sums_pipe_tailg_body(
     const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
     uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, int64_t n, uint32_t nchunks,
     uint32_t main_waves, uint32_t tail_full) {
@@ -552,8 +720,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void bloc
         if (c < nchunks) lane_chunk_sums<16, RSH_K1_TAIL_PF, false>(data, n, B, c, dl, seed, weak_out, strong_out);
         return;
     }
-    block_sums_pipe_body<false>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen, nullptr, n, nchunks,
-                                main_waves);
+    block_sums_pipe_body<false, false, false, DMA>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen,
+                                                   nullptr, n, nchunks, main_waves);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void block_sums_pipe_tailg_kernel(
+    const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
+    uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, int64_t n, uint32_t nchunks,
+    uint32_t main_waves, uint32_t tail_full) {
+    block_sums_pipe_tailg_body<true>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen, n, nchunks,
+                                     main_waves, tail_full);
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void block_sums_pipe_tailg_reg_kernel(
+    const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
+    uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, int64_t n, uint32_t nchunks,
+    uint32_t main_waves, uint32_t tail_full) {
+    block_sums_pipe_tailg_body<false>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen, n, nchunks,
+                                      main_waves, tail_full);
 }
 bool tail_gather_on() { return opt(OPT_K1_GATHER) != 0; }  // 0: leftover chunks one per lane (options.h)
 #ifdef RSH_KBENCH
@@ -562,19 +744,28 @@ __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_weakv_kernel(
     uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen) {
     block_sums_pipe_body<false, false, true>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen);
 }
+// the DMA form's diagnostic builds (block_sums_pipe_body, DIAG): 1 compute only, 2 loads only
+template <int DIAG>
+__global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_diag_kernel(
+    const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
+    uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen) {
+    block_sums_pipe_body<false, false, false, true, DIAG>(data, B, dl, seed, weak_out, strong_out, abort_flag,
+                                                          abort_gen);
+}
 #endif
 
 // Diagnostic (rsh_debug_k1_clock, MI355X_MICROARCH.md "DVFS give-back" item 6): the Generator's production K1 body
 // with each wave's shader-clock (s_memtime) and 100 MHz (s_memrealtime) ticks stamped around it and summed over the
 // launch; their quotient x 100 MHz is the clock the chip held under this load.  Only this instantiation stamps: the
 // production kernels never execute a stamp.  Whole coalesced waves only (n = 64 k B, B % 128 == 0).
+template <bool DMA>
 __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_clock_kernel(
     const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
     uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, int64_t n, uint32_t nchunks,
     unsigned long long* __restrict__ clk) {
     const uint64_t c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-    block_sums_pipe_body<false>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen, nullptr, n, nchunks,
-                                0xFFFFFFFFu);
+    block_sums_pipe_body<false, false, false, DMA>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen,
+                                                   nullptr, n, nchunks, 0xFFFFFFFFu);
     const uint64_t c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
     if (threadIdx.x == 0) {
         atomicAdd(&clk[0], (unsigned long long)(c1 - c0));
@@ -586,9 +777,13 @@ hipError_t launch_k1_clock(const uint8_t* d_data, int64_t n, uint32_t B, uint32_
                            int32_t* d_weak, uint8_t* d_strong, unsigned long long* d_clk, hipStream_t s) {
     if (B == 0 || B % 128 != 0 || n <= 0 || n % (64 * (int64_t)B) != 0 || dl > 16) return hipErrorInvalidValue;
     const uint32_t nchunks = (uint32_t)(n / B), waves = nchunks / 64;
-    const size_t wave_lds = 64 * 9 * sizeof(uint4);
-    hipLaunchKernelGGL(block_sums_pipe_clock_kernel, dim3(waves), dim3(64), 2 * wave_lds, s, d_data, B, dl, seed_word,
-                       d_weak, d_strong, never_word(), -1, n, nchunks, d_clk);
+    // the form the production launch of this buffer takes (launch_block_sums_variant)
+    if (k1_dma_on() && reinterpret_cast<uintptr_t>(d_data) % 16 == 0)
+        hipLaunchKernelGGL(block_sums_pipe_clock_kernel<true>, dim3(waves), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B, dl,
+                           seed_word, d_weak, d_strong, never_word(), -1, n, nchunks, d_clk);
+    else
+        hipLaunchKernelGGL(block_sums_pipe_clock_kernel<false>, dim3(waves), dim3(64), 2 * 64 * 9 * sizeof(uint4), s,
+                           d_data, B, dl, seed_word, d_weak, d_strong, never_word(), -1, n, nchunks, d_clk);
     return hipGetLastError();
 }
 #ifndef RSH_K1_SHIFT_VGPR
@@ -873,7 +1068,24 @@ hipError_t launch_block_sums_variant(int variant, const uint8_t* d_data, int64_t
     if (nchunks == 0) return hipSuccess;
     const uintptr_t addr = reinterpret_cast<uintptr_t>(d_data);
     const uint32_t nst = B >> 7;
+    bool dma_on = k1_dma_on();
 #ifdef RSH_KBENCH
+    if (variant == 1020 || variant == 1021) {  // the production launch in the DMA (1020) / register-staged (1021) form
+        dma_on = variant == 1020;
+        variant = -1;
+    }
+    if (variant == 1023 || variant == 1024) {  // the DMA form compute only / loads only (whole waves, 16-B aligned)
+        if ((B % 128) != 0 || nst < 4 || nst > 1024 || n != (int64_t)nchunks * B || nchunks % 64 != 0 || (addr % 16) != 0)
+            return hipErrorInvalidValue;
+        const int* word = abort_flag ? abort_flag : never_word();
+        if (variant == 1023)
+            hipLaunchKernelGGL(block_sums_pipe_diag_kernel<1>, dim3(nchunks / 64), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
+                               dl, seed_word, d_weak, d_strong, word, abort_flag ? abort_gen : -1);
+        else
+            hipLaunchKernelGGL(block_sums_pipe_diag_kernel<2>, dim3(nchunks / 64), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
+                               dl, seed_word, d_weak, d_strong, word, abort_flag ? abort_gen : -1);
+        return hipGetLastError();
+    }
     if (variant == 1010) {  // the VALU weak-sum form over whole waves (kbench shapes: n = 64 k B, 128-B aligned)
         if ((B % 128) != 0 || nst < 4 || nst > 1024 || n != (int64_t)nchunks * B || nchunks % 64 != 0 || (addr % 128) != 0)
             return hipErrorInvalidValue;
@@ -948,13 +1160,21 @@ hipError_t launch_block_sums_variant(int variant, const uint8_t* d_data, int64_t
         // still fits the chip's slots (2 per SIMD)
         const uint32_t tail_full = nfullc - 64 * waves, tail_short = nchunks - nfullc;
         const uint32_t gwaves = (tail_full + 63) / 64 + (tail_short + 63) / 64;
+        // the DMA form where every wave's base (d_data + 64 k B) is 16-B aligned: its loads write whole 16-B LDS slots
+        const bool dma = dma_on && (addr % 16) == 0;
         if (tail_full > 0 && tail_gather_on() && (gwaves == tail_waves || waves + gwaves <= 2 * 4 * kCUs)) {
-            k1_launch(block_sums_pipe_tailg_kernel, dim3(waves + gwaves), dim3(64), (uint32_t)(2 * wave_lds), s, d_data,
-                      B, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, n, nchunks, waves, tail_full);
+            // LDS: the gathered waves' two 9-slot buffers (above the DMA form's two 8 KiB slots)
+            k1_launch(dma ? block_sums_pipe_tailg_kernel : block_sums_pipe_tailg_reg_kernel, dim3(waves + gwaves),
+                      dim3(64), (uint32_t)(2 * wave_lds), s, d_data, B, dl, seed_word, d_weak, d_strong, abort_flag,
+                      abort_gen, n, nchunks, waves, tail_full);
             return hipGetLastError();
         }
-        k1_launch(block_sums_pipe_kernel<false>, dim3(waves + tail_waves), dim3(64), (uint32_t)(2 * wave_lds), s,
-                  d_data, B, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves);
+        if (dma)
+            k1_launch(block_sums_pipe_kernel<false>, dim3(waves + tail_waves), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
+                      dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves);
+        else
+            k1_launch(block_sums_pipe_reg_kernel<false>, dim3(waves + tail_waves), dim3(64), (uint32_t)(2 * wave_lds), s,
+                      d_data, B, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves);
         return hipGetLastError();
     }
     // one lane per chunk
@@ -1103,7 +1323,7 @@ static const int* never_word() {
 // nothing), then the lane waves (short chunks and odd shapes, one chunk per lane), instead of the per-lane
 // kernel queued behind the groups (a wave of it takes one chunk's serial time: ~2 ms at B = 128 KiB).
 // Register budget 256 as block_sums_pipe_tailg_kernel.
-template <int ALIGN>
+template <int ALIGN, bool DMA = true>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void block_sums_pipe_multi_g_kernel(
     const K1Group* __restrict__ groups, uint32_t ngroups, const K1Lane* __restrict__ lanes, uint32_t seed,
     const int* abort_flag, int abort_gen) {
@@ -1122,32 +1342,52 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void bloc
                                                            0xFFFFFFFFu, nullptr, g.count);
         return;
     }
-    block_sums_pipe_body<true>(nullptr, 0u, 0u, seed, nullptr, nullptr, abort_flag, abort_gen, groups);
+    block_sums_pipe_body<true, false, false, DMA>(nullptr, 0u, 0u, seed, nullptr, nullptr, abort_flag, abort_gen, groups);
 }
 
 hipError_t launch_block_sums_batch(const K1Group* d_groups, uint32_t ngroups, const K1Lane* d_lanes, uint32_t nlanes,
                                    int lane_align, uint32_t seed_word, hipStream_t s, const int* abort_flag,
                                    int abort_gen, bool partial) {
-    const size_t lb = 2 * 64 * 9 * sizeof(uint4);
+    const size_t lb = 2 * 64 * 9 * sizeof(uint4);  // a gathered wave's buffers (the DMA form's slots are 2 x 8 KiB)
+    // the planners cut groups only at 16-B aligned bases (plan_block_sums_batch / _files), so every group may take
+    // the DMA form; files at other bases are lanes
+    const bool dma = k1_dma_on();
     if (!abort_flag && (abort_flag = never_word()) != nullptr) abort_gen = -1;  // see never_word
     if (!abort_flag) return hipErrorOutOfMemory;  // never_word() failed: no uncached word for the pinned K1
     // partial groups, or lanes beside groups: one launch (option k1_gather = 0: the lanes as a second launch)
     if (partial || (tail_gather_on() && nlanes > 0 && ngroups > 0)) {
         const dim3 grid(ngroups + nlanes);
-        if (lane_align == 16)
-            hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<16>), grid, dim3(64), lb, s, d_groups, ngroups, d_lanes,
-                               seed_word, abort_flag, abort_gen);
-        else if (lane_align == 4)
-            hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<4>), grid, dim3(64), lb, s, d_groups, ngroups, d_lanes,
-                               seed_word, abort_flag, abort_gen);
-        else
-            hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<1>), grid, dim3(64), lb, s, d_groups, ngroups, d_lanes,
-                               seed_word, abort_flag, abort_gen);
+        if (dma) {
+            if (lane_align == 16)
+                hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<16>), grid, dim3(64), lb, s, d_groups, ngroups,
+                                   d_lanes, seed_word, abort_flag, abort_gen);
+            else if (lane_align == 4)
+                hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<4>), grid, dim3(64), lb, s, d_groups, ngroups, d_lanes,
+                                   seed_word, abort_flag, abort_gen);
+            else
+                hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<1>), grid, dim3(64), lb, s, d_groups, ngroups, d_lanes,
+                                   seed_word, abort_flag, abort_gen);
+        } else {
+            if (lane_align == 16)
+                hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<16, false>), grid, dim3(64), lb, s, d_groups, ngroups,
+                                   d_lanes, seed_word, abort_flag, abort_gen);
+            else if (lane_align == 4)
+                hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<4, false>), grid, dim3(64), lb, s, d_groups, ngroups,
+                                   d_lanes, seed_word, abort_flag, abort_gen);
+            else
+                hipLaunchKernelGGL((block_sums_pipe_multi_g_kernel<1, false>), grid, dim3(64), lb, s, d_groups, ngroups,
+                                   d_lanes, seed_word, abort_flag, abort_gen);
+        }
         return hipGetLastError();
     }
-    if (ngroups > 0)
-        hipLaunchKernelGGL((block_sums_pipe_kernel<true>), dim3(ngroups), dim3(64), lb, s, nullptr, 0u, 0u, seed_word,
-                           nullptr, nullptr, abort_flag, abort_gen, d_groups);
+    if (ngroups > 0) {
+        if (dma)
+            hipLaunchKernelGGL((block_sums_pipe_kernel<true>), dim3(ngroups), dim3(64), 2 * K1_DMA_STAGE, s, nullptr, 0u,
+                               0u, seed_word, nullptr, nullptr, abort_flag, abort_gen, d_groups);
+        else
+            hipLaunchKernelGGL((block_sums_pipe_reg_kernel<true>), dim3(ngroups), dim3(64), lb, s, nullptr, 0u, 0u,
+                               seed_word, nullptr, nullptr, abort_flag, abort_gen, d_groups);
+    }
     if (nlanes > 0) {
         if (lane_align == 16)
             hipLaunchKernelGGL((block_sums_lane_batch_kernel<16>), dim3(nlanes), dim3(64), 0, s, d_lanes, seed_word);

@@ -43,6 +43,7 @@ enum Opt : int {
     OPT_TOKENS_PIECE,      // ... bytes per pinned staging buffer (two of them: one filled while the other is copied out)
     OPT_SUMS_PIECE,        // rsh_sums_*_device / rsh_*_batch_wire: table bytes per pinned staging piece (one launch each)
     OPT_TOKENS_RUNS,       // rsh_receiver_combine_resident: run records per launch of the token walk (a full list: relaunch)
+    OPT_K1_DMA,            // 1: the pipelined K1's main waves load straight into LDS at 16-B aligned bases; 0: register staging
     OPT_COUNT
 };
 
@@ -59,7 +60,7 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"segment_bytes", 16LL << 30}, {"md5_width", 0},    {"chain_helpers", -1},
     {"chain_map_bytes", 1LL << 30}, {"time_gen", 1},    {"batch_warm", 128},
     {"fault_inject", 0},        {"tokens_span", 256LL << 10}, {"tokens_piece", 8LL << 20},
-    {"sums_piece", 32LL << 20}, {"tokens_runs", 64LL << 10},
+    {"sums_piece", 32LL << 20}, {"tokens_runs", 64LL << 10}, {"k1_dma", 1},
 };
 
 inline const OptInfo* opt_info() { return kOpts; }

@@ -8,6 +8,10 @@
 // variant 1003: the segmented launch (the Sender's prefix + phase speculation kernel) over the buffer.
 // variant 1005: the production batch planner over ragged files (below).
 // variant 1010: the pipelined K1 with its weak sums on the VALU (v_dot4) instead of the MFMAs (energy A/B).
+// variant 1020 / 1021: the production abortable launch in the DMA form / the register-staged form (option k1_dma);
+// variant 1022: the two interleaved launch by launch in one process.
+// variant 1023 / 1024: the DMA form's diagnostic builds, compute only (a zero-record descriptor drops every load) /
+// loads only (no MD5, no MFMAs); their sums are not the chunks' (parity MISMATCH is expected).
 // (The rejected K1 forms measured in rounds 1-4 -- the coalesced kernel's MD5 step forms, LDS-DMA stages, 4 waves per
 // SIMD, persistent waves, no-LDS loads -- were deleted after their A/Bs; DESIGN.md sec. 4 keeps the numbers.)
 #include <hip/hip_runtime.h>
@@ -417,7 +421,8 @@ int main(int argc, char** argv) {
             return rsh::launch_block_sums_batch(d_groups, (uint32_t)groups.size(), d_lanes, (uint32_t)lanes.size(),
                                                 lane_align, 0x04030201u, s);
         if (v == 1000) return rsh::launch_block_sums_variant(-1, d, n, B, C, dl, 0x04030201u, w, sx, s, abort_word, 1);
-        if (v == 1010) return rsh::launch_block_sums_variant(1010, d, n, B, C, dl, 0x04030201u, w, sx, s, abort_word, 1);
+        if (v == 1010 || (v >= 1020 && v <= 1024 && v != 1022))
+            return rsh::launch_block_sums_variant(v, d, n, B, C, dl, 0x04030201u, w, sx, s, abort_word, 1);
         if (v == 1001) return rsh::launch_block_sums(d, n, B, C, dl, 0x04030201u, w, sx, s);  // the production entry
         return rsh::launch_block_sums_variant(v, d, n, B, C, dl, 0x04030201u, w, sx, s);
     };
@@ -426,6 +431,35 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e1));
     for (int a = 5; a < argc; ++a) {
         const int v = atoi(argv[a]);
+        if (v == 1022) {  // 1020 and 1021 interleaved, launch by launch: the same clock and HBM state for both forms
+            float best[2] = {1e30f, 1e30f}, tot[2] = {0, 0};
+            bool same[2];
+            for (int f = 0; f < 2; ++f) {
+                CK(hipMemset(w, 0, C * 4));
+                CK(launch(1020 + f));
+                CK(hipStreamSynchronize(s));
+                CK(hipMemcpy(hw.data(), w, C * 4, hipMemcpyDeviceToHost));
+                CK(hipMemcpy(hs.data(), sx, (size_t)C * dl, hipMemcpyDeviceToHost));
+                same[f] = hw == hw0 && hs == hs0;
+            }
+            for (int r = 0; r < 2 * reps; ++r) {
+                const int f = r & 1;
+                CK(hipEventRecord(e0, s));
+                CK(launch(1020 + f));
+                CK(hipEventRecord(e1, s));
+                CK(hipEventSynchronize(e1));
+                float ms;
+                CK(hipEventElapsedTime(&ms, e0, e1));
+                best[f] = ms < best[f] ? ms : best[f];
+                tot[f] += ms;
+            }
+            for (int f = 0; f < 2; ++f)
+                printf("variant %d (interleaved)  n=%lld B=%u C=%u  avg %.3f ms  best %.3f ms  %.1f GB/s  parity=%s\n",
+                       1020 + f, (long long)n, B, C, tot[f] / reps, best[f], n / (tot[f] / reps / 1e3) / 1e9,
+                       same[f] ? "ok" : "MISMATCH");
+            fflush(stdout);
+            continue;
+        }
         CK(hipMemset(w, 0, C * 4));
         CK(launch(v));
         CK(hipStreamSynchronize(s));
