@@ -7,10 +7,15 @@
  * Tests force rare paths with them; a few are tunables: k1_gather, k1_shift,
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
- * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma.
+ * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio.
  *
  * k1_dma = 1 (default): the main waves of the pipelined K1 stream their stages from HBM straight into LDS wherever
  * every wave's base is 16-B aligned; 0: the register-staged form at every base (the A/B partner, from one library).
+ *
+ * k1_prio = k in 1 .. 31: in a single-file K1 launch that fits one round of the chip's wave slots (at most 2048 main
+ * waves), the two main waves that share a SIMD take VALU issue priority 1 in turn, 2^k stages (of 128 B per chunk) at
+ * a time, by the parity of their wave slot, so that they end together; 0: both stay at priority 0.  k + 32: in
+ * launches of any size (tests, A/B runs).  The batched launches never alternate.
  *
  * fault_inject is a bit set: bit 0 (1) fails a segment or Receiver pass's HBM allocation (RSH_E_NOMEM), bit 1 (2) a
  * segment pass's copies (RSH_E_DEVICE); bit 2 (4) limits both to member 1 of a multi-context call; bit 3 (8) limits
@@ -56,6 +61,23 @@ int rsh_debug_streams_busy(rsh_ctx* ctx, int32_t* mask);
  * reports it beside the headline (k1_clock_ghz). */
 int rsh_debug_k1_clock(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t block_length, int32_t reps,
                        double* clock_ghz);
+
+/* Per-wave times of the production K1: one launch of the stamped diagnostic instantiation (as rsh_debug_k1_clock's)
+ * over the device bytes [d_data, d_data + n) (n a multiple of 64 * block_length, block_length a multiple of 128 in
+ * 512 .. 131072) writes one record per wave, wave w = chunks [64 w, 64 w + 64), into records[0, n / (64 *
+ * block_length)) (host memory; RSH_E_NOSPACE when cap is smaller).  prio: the turn length of this launch (0 .. 31, as
+ * k1_prio's k), -1 what the option gives a production launch of this size.  d_weak, d_strong (device, n / block_length sums of 4 and 16 bytes; NULL: scratch of the call's
+ * own): the launch's sums, the production K1's, since no value is computed from a stamp. */
+typedef struct {
+    uint32_t hw_id;      /* hwreg(HW_REG_HW_ID): wave slot bits 3:0, SIMD 5:4, CU 11:8, SH 12, SE 15:13 */
+    uint32_t xcc_id;     /* hwreg(HW_REG_XCC_ID): the XCD in bits 3:0 */
+    uint64_t real_start; /* s_memrealtime (100 MHz) at the wave's start and end */
+    uint64_t real_end;
+    uint64_t clk_start;  /* s_memtime (shader clock) at the wave's start and end */
+    uint64_t clk_end;
+} rsh_k1_wave_time;
+int rsh_debug_k1_wave_times(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t block_length, int32_t prio,
+                            rsh_k1_wave_time* records, int64_t cap, int32_t* d_weak, uint8_t* d_strong);
 
 /* The swizzle of the pipelined K1's DMA-form LDS image (a stage: 64 chunks x eight 16-B pieces, slot p of chunk c at
  * byte 128 c + 16 p), without a device.  what = 0: the piece that the lane filling slot `index` of `chunk` fetches;

@@ -607,6 +607,35 @@ int rsh_debug_k1_clock(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t bloc
     return RSH_OK;
 }
 
+static_assert(sizeof(rsh_k1_wave_time) == sizeof(rsh::K1WaveTime) && sizeof(rsh_k1_wave_time) == 40,
+              "rsh_k1_wave_time is the device record");
+
+int rsh_debug_k1_wave_times(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t block_length, int32_t prio,
+                            rsh_k1_wave_time* records, int64_t cap, int32_t* d_weak, uint8_t* d_strong) {
+    if (!ctx || !d_data || !records || block_length < 512 || block_length > 131072 || block_length % 128 != 0 ||
+        n <= 0 || n % (64 * (int64_t)block_length) != 0 || prio < -1 || prio > 31)
+        return RSH_E_INVAL;
+    const int64_t C = n / block_length, waves = C / 64;
+    if (cap < waves) return RSH_E_NOSPACE;
+    RSH_HIP(hipSetDevice(ctx->device));
+    void *w = nullptr, *st = nullptr, *rec = nullptr;
+    hipError_t e = hipSuccess;
+    if (!d_weak) e = hipMalloc(&w, (size_t)C * 4);
+    if (e == hipSuccess && !d_strong) e = hipMalloc(&st, (size_t)C * 16);
+    if (e == hipSuccess) e = hipMalloc(&rec, (size_t)waves * sizeof(rsh::K1WaveTime));
+    if (e == hipSuccess)
+        e = rsh::launch_k1_clock(static_cast<const uint8_t*>(d_data), n, (uint32_t)block_length, 16, 0x04030201u,
+                                 d_weak ? d_weak : static_cast<int32_t*>(w), d_strong ? d_strong : static_cast<uint8_t*>(st),
+                                 nullptr, ctx->stream, prio, static_cast<rsh::K1WaveTime*>(rec));
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(records, rec, (size_t)waves * sizeof(rsh::K1WaveTime), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    for (void* p : {w, st, rec})
+        if (p) (void)hipFree(p);
+    RSH_HIP(e);
+    return RSH_OK;
+}
+
 int rsh_fill_splitmix_device(rsh_ctx* ctx, void* d_out, int64_t n, uint64_t key, int64_t byte_offset) {
     if (!ctx || (n > 0 && !d_out) || n < 0 || byte_offset < 0) return RSH_E_INVAL;
     RSH_HIP(hipSetDevice(ctx->device));

@@ -116,6 +116,15 @@ constexpr uint32_t k1_dma_piece(uint32_t c, uint32_t p) { return p ^ ((c >> 1) &
 constexpr uint32_t k1_dma_slot(uint32_t c, uint32_t k) { return k ^ ((c >> 1) & 7u); }
 constexpr uint32_t k1_dma_lds_byte(uint32_t c, uint32_t slot) { return 128u * c + 16u * slot; }
 bool k1_dma_on();  // option k1_dma = 0: the register-staged form at every base
+// option k1_prio (block_sums_pipe_body, PRIO) for a launch of `waves` main waves: 0 off (always when the launch needs
+// more than one round of the chip's wave slots), else log2 of the stages a main wave keeps one issue priority
+uint32_t k1_prio(uint32_t waves);
+// One wave of the diagnostic K1 (launch_k1_clock with d_rec; rsh_k1_wave_time of rsync_hip_debug.h)
+struct K1WaveTime {
+    uint32_t hw_id, xcc_id;   // hwreg(HW_REG_HW_ID), hwreg(HW_REG_XCC_ID)
+    uint64_t real0, real1;    // s_memrealtime (100 MHz) before and after the body
+    uint64_t clk0, clk1;      // s_memtime (shader clock) before and after the body
+};
 // partial: some groups have count < 64 (plan_block_sums_files) -- they run as gathered waves of the same launch
 hipError_t launch_block_sums_batch(const K1Group* d_groups, uint32_t ngroups, const K1Lane* d_lanes, uint32_t nlanes,
                                    int lane_align, uint32_t seed_word, hipStream_t s, const int* abort_flag = nullptr,
@@ -471,9 +480,11 @@ struct ChainFile {
     const uint8_t* dup;                // per chunk: 1 when another chunk has its weak sum (launch_chunk_index)
 };
 // Diagnostic: the Generator's K1 over n = 64 k B bytes with per-wave clock stamps summed into d_clk[0] (shader clock
-// ticks) and d_clk[1] (100 MHz ticks); the production kernels never stamp.
+// ticks) and d_clk[1] (100 MHz ticks); the production kernels never stamp.  d_rec != null: one K1WaveTime per wave
+// (n / (64 B) of them) instead of the sums.  prio: the PRIO argument of the body, < 0 the option's value.
 hipError_t launch_k1_clock(const uint8_t* d_data, int64_t n, uint32_t B, uint32_t dl, uint32_t seed_word,
-                           int32_t* d_weak, uint8_t* d_strong, unsigned long long* d_clk, hipStream_t s);
+                           int32_t* d_weak, uint8_t* d_strong, unsigned long long* d_clk, hipStream_t s,
+                           int32_t prio = -1, K1WaveTime* d_rec = nullptr);
 // help (phase 0): the files' ChainHelp array, or null (no map); helpers: extra workgroups beyond nfiles that only
 // map; finished walks map too.  abort_gen is also the map's generation.
 // timed: the walks read the wall clock for their section timers (scan_trace's report; ChainOut::t_*).

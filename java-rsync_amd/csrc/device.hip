@@ -308,7 +308,8 @@ __device__ __forceinline__ void md5_stream_block(Md5State& st, const uint32_t (&
 // DIAG (kbench only, the DMA form's diagnostic builds; their sums are not the chunks'): 1 = compute only -- the
 // descriptor has zero records, so the range check drops every load while the instruction stream and the waits stay
 // (variant 1023); 2 = loads only -- the stage's words are folded with one XOR per 16 bytes instead of MD5 and the
-// MFMAs (variant 1024).
+// MFMAs (variant 1024); 3 = the production kernel with the no-nop MD5 steps (md5_asm_nonop.inc, variant 1025: its sums
+// are the chunks').
 template <bool MULTI = false, bool GATHER = false, bool WEAKV = false, bool DMA = false, int DIAG = 0>
 __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__ data, uint32_t B, uint32_t dl,
                                                              uint32_t seed, int32_t* __restrict__ weak_out,
@@ -318,7 +319,8 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
                                                              int64_t n = 0, uint32_t nchunks = 0,
                                                              uint32_t main_waves = 0xFFFFFFFFu,
                                                              const K1Tail* __restrict__ gt = nullptr,
-                                                             uint32_t gcnt = 0, uint32_t gsel = 0xFFFFFFFFu) {
+                                                             uint32_t gcnt = 0, uint32_t gsel = 0xFFFFFFFFu,
+                                                             uint32_t prio = 0) {
     constexpr int ROW = 9;
     constexpr int BUF = 64 * ROW;  // uint4 slots per LDS buffer
     constexpr int TAIL_PF = RSH_K1_TAIL_PF;
@@ -366,6 +368,36 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
         c0 = 0;
     }
     const uint32_t nst = B >> 7;  // host guarantees nst >= 4
+    // PRIO (option k1_prio, the main waves; 0 = off): a SIMD's two waves share its VALU issue by priority, then age,
+    // so at equal priority the older one runs near a lone wave's rate and the younger one ends the launch alone
+    // (0.25 ms later at the headline shape).  Each wave reads its slot parity once (bit 0 of HW_ID's
+    // wave id) and, once per steady iteration, takes priority 1 while ((stage >> prio) ^ parity) & 1 and priority 0
+    // otherwise: the two are favoured in turn and end within one period of each other.  Two waves of equal parity
+    // toggle in phase and age decides, as without it.  Off, the same six scalar instructions run and set priority 0
+    // every time.  Levels 0 and 1 only: the resolver's kernels stay ahead at 3.  Not in the batched form (MULTI): its
+    // launches run many rounds of waves, partners are at unrelated stages, and config 4 lost 0.2-0.5 % with it.
+    constexpr bool PRIO = !GATHER && !MULTI;
+    [[maybe_unused]] uint32_t par = 0;
+    if constexpr (PRIO) {
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 1)" : "=s"(par));
+        par = prio ? par : 0u;
+    }
+    auto take_turn = [&]([[maybe_unused]] uint32_t stg) __attribute__((always_inline)) {
+        if constexpr (PRIO) {
+            uint32_t t;
+            asm volatile(
+                "s_lshr_b32 %0, %1, %2\n\t"
+                "s_xor_b32 %0, %0, %3\n\t"
+                "s_bitcmp1_b32 %0, 0\n\t"
+                "s_setprio 0\n\t"
+                "s_cbranch_scc0 1f\n\t"
+                "s_setprio 1\n"
+                "1:"
+                : "=&s"(t)
+                : "s"(stg), "s"(prio), "s"(par)
+                : "scc");
+        }
+    };
     const int wr0 = (l >> 3) * ROW + (l & 7);
     const int rd0 = l * ROW;
 
@@ -395,6 +427,12 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
         }
         uint32_t m[16];
         unpack(w, m);
+#ifdef RSH_KBENCH
+        if constexpr (DIAG == 3) {  // the steps without their s_nop 0
+            md5_compress_rot16(st, m);
+            return;
+        }
+#endif
         md5_stream_block(st, m);
     };
     [[maybe_unused]] int32_t vs1 = 0, vu = 0;  // WEAKV: the lane's own sums
@@ -526,6 +564,7 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
         uint32_t s = 0;
         // steady state, branch-free: exactly two stages of loads in flight below each refill
         for (; s + 5 <= nst && flag != abort_gen; s += 2) {
+            take_turn(s);
             stage(std::integral_constant<int, 0>{}, s, true, true, true);
             stage(std::integral_constant<int, 1>{}, s + 1, true, true, false);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(flag));
@@ -604,6 +643,7 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
     // operation in flight (they only get stricter).
     int flag = 0;
     for (; s + 5 <= nst && flag != abort_gen; s += 2) {
+        take_turn(s);
         asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(flag) : "s"(abort_flag));
         stage(std::integral_constant<int, 0>{}, s, true, true);
         stage(std::integral_constant<int, 1>{}, s + 1, true, true);
@@ -615,6 +655,7 @@ __device__ __forceinline__ void block_sums_pipe_body(const uint8_t* __restrict__
         if (s + 1 < nst) stage(std::integral_constant<int, 1>{}, s + 1, s + 2 < nst, s + 4 < nst);
     }
     }  // !DMA
+    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);  // the closing block and the stores at the launch's own level
     {
         const uint64_t bits = ((uint64_t)B + 4) * 8;
         uint32_t m[16] = {seed, 0x80u, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, (uint32_t)bits, (uint32_t)(bits >> 32)};
@@ -673,6 +714,15 @@ constexpr bool k1_dma_swizzle_ok() {
 }
 static_assert(k1_dma_swizzle_ok(), "K1 DMA image: bank conflict or slot / piece mismatch");
 bool k1_dma_on() { return opt(OPT_K1_DMA) != 0; }
+// option k1_prio (block_sums_pipe_body, PRIO) for a launch of `waves` main waves: 0 off, else log2 of the stages a wave
+// keeps one priority.  Only where the launch fits one round of the chip's slots: there every wave starts with its
+// partner and carries the same work.  In later rounds partners are at unrelated stages (kbench, 16 GiB at B = 8 KiB,
+// 16 rounds: 2.90 ms off, 2.95 ms on).  Option bit 5 (+32; tests and A/B runs): at every wave count.
+constexpr uint32_t kK1Slots = 2 * 4 * 256;  // 256 CUs x 4 SIMDs x 2 waves (the occupancy pin)
+uint32_t k1_prio(uint32_t waves) {
+    const int64_t v = opt(OPT_K1_PRIO);
+    return v > 0 && (waves <= kK1Slots || (v & 32)) ? (uint32_t)(v & 31) : 0u;
+}
 
 // block_sums_pipe_kernel: the main waves in the DMA form (16-B aligned bases, option k1_dma);
 // block_sums_pipe_reg_kernel: the register-staged form (any base, k1_dma = 0).
@@ -683,18 +733,18 @@ __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_kernel(const 
                                                              const int* abort_flag = nullptr, int abort_gen = 0,
                                                              const K1Group* __restrict__ groups = nullptr,
                                                              int64_t n = 0, uint32_t nchunks = 0,
-                                                             uint32_t main_waves = 0xFFFFFFFFu) {
+                                                             uint32_t main_waves = 0xFFFFFFFFu, uint32_t prio = 0) {
     block_sums_pipe_body<MULTI, false, false, true>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen,
-                                                    groups, n, nchunks, main_waves);
+                                                    groups, n, nchunks, main_waves, nullptr, 0, 0xFFFFFFFFu, prio);
 }
 template <bool MULTI = false>
 __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_reg_kernel(
     const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
     uint8_t* __restrict__ strong_out, const int* abort_flag = nullptr, int abort_gen = 0,
     const K1Group* __restrict__ groups = nullptr, int64_t n = 0, uint32_t nchunks = 0,
-    uint32_t main_waves = 0xFFFFFFFFu) {
+    uint32_t main_waves = 0xFFFFFFFFu, uint32_t prio = 0) {
     block_sums_pipe_body<MULTI>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen, groups, n, nchunks,
-                                main_waves);
+                                main_waves, nullptr, 0, 0xFFFFFFFFu, prio);
 }
 // The production K1 with the partial last wave's full-length chunks as a gathered coalesced wave (the tail
 // waves past main_waves: ceil(tail_full / 64) gathered ones, then the short last chunk, if any, per lane).  A
@@ -706,7 +756,7 @@ template <bool DMA>
 __device__ __forceinline__ void block_sums_pipe_tailg_body(
     const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
     uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, int64_t n, uint32_t nchunks,
-    uint32_t main_waves, uint32_t tail_full) {
+    uint32_t main_waves, uint32_t tail_full, uint32_t prio) {
     if (blockIdx.x >= main_waves) {
         const uint32_t tw = blockIdx.x - main_waves, ngw = (tail_full + 63u) / 64u;
         if (tw < ngw) {
@@ -721,21 +771,21 @@ __device__ __forceinline__ void block_sums_pipe_tailg_body(
         return;
     }
     block_sums_pipe_body<false, false, false, DMA>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen,
-                                                   nullptr, n, nchunks, main_waves);
+                                                   nullptr, n, nchunks, main_waves, nullptr, 0, 0xFFFFFFFFu, prio);
 }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void block_sums_pipe_tailg_kernel(
     const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
     uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, int64_t n, uint32_t nchunks,
-    uint32_t main_waves, uint32_t tail_full) {
+    uint32_t main_waves, uint32_t tail_full, uint32_t prio) {
     block_sums_pipe_tailg_body<true>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen, n, nchunks,
-                                     main_waves, tail_full);
+                                     main_waves, tail_full, prio);
 }
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void block_sums_pipe_tailg_reg_kernel(
     const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
     uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, int64_t n, uint32_t nchunks,
-    uint32_t main_waves, uint32_t tail_full) {
+    uint32_t main_waves, uint32_t tail_full, uint32_t prio) {
     block_sums_pipe_tailg_body<false>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen, n, nchunks,
-                                      main_waves, tail_full);
+                                      main_waves, tail_full, prio);
 }
 bool tail_gather_on() { return opt(OPT_K1_GATHER) != 0; }  // 0: leftover chunks one per lane (options.h)
 #ifdef RSH_KBENCH
@@ -744,46 +794,65 @@ __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_weakv_kernel(
     uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen) {
     block_sums_pipe_body<false, false, true>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen);
 }
-// the DMA form's diagnostic builds (block_sums_pipe_body, DIAG): 1 compute only, 2 loads only
+// the DMA form's diagnostic builds (block_sums_pipe_body, DIAG): 1 compute only, 2 loads only, 3 no-nop MD5 steps
 template <int DIAG>
 __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_diag_kernel(
     const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
-    uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen) {
+    uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, uint32_t prio) {
     block_sums_pipe_body<false, false, false, true, DIAG>(data, B, dl, seed, weak_out, strong_out, abort_flag,
-                                                          abort_gen);
+                                                          abort_gen, nullptr, 0, 0, 0xFFFFFFFFu, nullptr, 0, 0xFFFFFFFFu,
+                                                          prio);
 }
 #endif
 
 // Diagnostic (rsh_debug_k1_clock, MI355X_MICROARCH.md "DVFS give-back" item 6): the Generator's production K1 body
 // with each wave's shader-clock (s_memtime) and 100 MHz (s_memrealtime) ticks stamped around it and summed over the
-// launch; their quotient x 100 MHz is the clock the chip held under this load.  Only this instantiation stamps: the
+// launch; their quotient x 100 MHz is the clock the chip held under this load.  Only this kernel stamps: the
 // production kernels never execute a stamp.  Whole coalesced waves only (n = 64 k B, B % 128 == 0).
-template <bool DMA>
+// WAVES (rsh_debug_k1_wave_times): instead of the summed ticks, one K1WaveTime per wave -- where it ran (HW_ID, XCC_ID) and
+// its four stamps -- into rec[blockIdx.x], a buffer nothing else reads.  No output value is computed from a stamp.
+template <bool DMA, bool WAVES = false>
 __global__ __launch_bounds__(64) K1_PIPE_ATTR void block_sums_pipe_clock_kernel(
     const uint8_t* __restrict__ data, uint32_t B, uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out,
     uint8_t* __restrict__ strong_out, const int* abort_flag, int abort_gen, int64_t n, uint32_t nchunks,
-    unsigned long long* __restrict__ clk) {
+    unsigned long long* __restrict__ clk, uint32_t prio, K1WaveTime* __restrict__ rec) {
     const uint64_t c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     block_sums_pipe_body<false, false, false, DMA>(data, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen,
-                                                   nullptr, n, nchunks, 0xFFFFFFFFu);
+                                                   nullptr, n, nchunks, 0xFFFFFFFFu, nullptr, 0, 0xFFFFFFFFu, prio);
     const uint64_t c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0) {
+    if constexpr (WAVES) {
+        uint32_t hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        if (threadIdx.x == 0) rec[blockIdx.x] = K1WaveTime{hw, xcc, r0, r1, c0, c1};
+    } else if (threadIdx.x == 0) {
         atomicAdd(&clk[0], (unsigned long long)(c1 - c0));
         atomicAdd(&clk[1], (unsigned long long)(r1 - r0));
     }
 }
 
+// prio < 0: option k1_prio, as the production launch; d_clk (the summed ticks) or d_rec (one record per wave)
 hipError_t launch_k1_clock(const uint8_t* d_data, int64_t n, uint32_t B, uint32_t dl, uint32_t seed_word,
-                           int32_t* d_weak, uint8_t* d_strong, unsigned long long* d_clk, hipStream_t s) {
+                           int32_t* d_weak, uint8_t* d_strong, unsigned long long* d_clk, hipStream_t s, int32_t prio,
+                           K1WaveTime* d_rec) {
     if (B == 0 || B % 128 != 0 || n <= 0 || n % (64 * (int64_t)B) != 0 || dl > 16) return hipErrorInvalidValue;
+    if (d_rec && (B < 512 || B > 131072 || prio > 31)) return hipErrorInvalidValue;  // the pipelined K1's stage counts
     const uint32_t nchunks = (uint32_t)(n / B), waves = nchunks / 64;
+    const uint32_t p = prio < 0 ? k1_prio(waves) : (uint32_t)prio;
     // the form the production launch of this buffer takes (launch_block_sums_variant)
-    if (k1_dma_on() && reinterpret_cast<uintptr_t>(d_data) % 16 == 0)
-        hipLaunchKernelGGL(block_sums_pipe_clock_kernel<true>, dim3(waves), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B, dl,
-                           seed_word, d_weak, d_strong, never_word(), -1, n, nchunks, d_clk);
-    else
-        hipLaunchKernelGGL(block_sums_pipe_clock_kernel<false>, dim3(waves), dim3(64), 2 * 64 * 9 * sizeof(uint4), s,
-                           d_data, B, dl, seed_word, d_weak, d_strong, never_word(), -1, n, nchunks, d_clk);
+    const bool dma = k1_dma_on() && reinterpret_cast<uintptr_t>(d_data) % 16 == 0;
+    const uint32_t lds = dma ? 2 * K1_DMA_STAGE : 2 * 64 * 9 * sizeof(uint4);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(waves), dim3(64), lds, s, d_data, B, dl, seed_word, d_weak, d_strong,
+                           never_word(), -1, n, nchunks, d_clk, p, d_rec);
+    };
+    if (d_rec) {
+        if (dma) go(block_sums_pipe_clock_kernel<true, true>);
+        else go(block_sums_pipe_clock_kernel<false, true>);
+    } else {
+        if (dma) go(block_sums_pipe_clock_kernel<true>);
+        else go(block_sums_pipe_clock_kernel<false>);
+    }
     return hipGetLastError();
 }
 #ifndef RSH_K1_SHIFT_VGPR
@@ -1074,16 +1143,19 @@ hipError_t launch_block_sums_variant(int variant, const uint8_t* d_data, int64_t
         dma_on = variant == 1020;
         variant = -1;
     }
-    if (variant == 1023 || variant == 1024) {  // the DMA form compute only / loads only (whole waves, 16-B aligned)
+    if (variant >= 1023 && variant <= 1025) {  // the DMA form compute only / loads only / no-nop (whole waves, 16-B aligned)
         if ((B % 128) != 0 || nst < 4 || nst > 1024 || n != (int64_t)nchunks * B || nchunks % 64 != 0 || (addr % 16) != 0)
             return hipErrorInvalidValue;
         const int* word = abort_flag ? abort_flag : never_word();
         if (variant == 1023)
             hipLaunchKernelGGL(block_sums_pipe_diag_kernel<1>, dim3(nchunks / 64), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
-                               dl, seed_word, d_weak, d_strong, word, abort_flag ? abort_gen : -1);
-        else
+                               dl, seed_word, d_weak, d_strong, word, abort_flag ? abort_gen : -1, k1_prio(nchunks / 64));
+        else if (variant == 1024)
             hipLaunchKernelGGL(block_sums_pipe_diag_kernel<2>, dim3(nchunks / 64), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
-                               dl, seed_word, d_weak, d_strong, word, abort_flag ? abort_gen : -1);
+                               dl, seed_word, d_weak, d_strong, word, abort_flag ? abort_gen : -1, k1_prio(nchunks / 64));
+        else
+            hipLaunchKernelGGL(block_sums_pipe_diag_kernel<3>, dim3(nchunks / 64), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
+                               dl, seed_word, d_weak, d_strong, word, abort_flag ? abort_gen : -1, k1_prio(nchunks / 64));
         return hipGetLastError();
     }
     if (variant == 1010) {  // the VALU weak-sum form over whole waves (kbench shapes: n = 64 k B, 128-B aligned)
@@ -1162,19 +1234,20 @@ hipError_t launch_block_sums_variant(int variant, const uint8_t* d_data, int64_t
         const uint32_t gwaves = (tail_full + 63) / 64 + (tail_short + 63) / 64;
         // the DMA form where every wave's base (d_data + 64 k B) is 16-B aligned: its loads write whole 16-B LDS slots
         const bool dma = dma_on && (addr % 16) == 0;
+        const uint32_t prio = k1_prio(waves);
         if (tail_full > 0 && tail_gather_on() && (gwaves == tail_waves || waves + gwaves <= 2 * 4 * kCUs)) {
             // LDS: the gathered waves' two 9-slot buffers (above the DMA form's two 8 KiB slots)
             k1_launch(dma ? block_sums_pipe_tailg_kernel : block_sums_pipe_tailg_reg_kernel, dim3(waves + gwaves),
                       dim3(64), (uint32_t)(2 * wave_lds), s, d_data, B, dl, seed_word, d_weak, d_strong, abort_flag,
-                      abort_gen, n, nchunks, waves, tail_full);
+                      abort_gen, n, nchunks, waves, tail_full, prio);
             return hipGetLastError();
         }
         if (dma)
             k1_launch(block_sums_pipe_kernel<false>, dim3(waves + tail_waves), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
-                      dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves);
+                      dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves, prio);
         else
             k1_launch(block_sums_pipe_reg_kernel<false>, dim3(waves + tail_waves), dim3(64), (uint32_t)(2 * wave_lds), s,
-                      d_data, B, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves);
+                      d_data, B, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves, prio);
         return hipGetLastError();
     }
     // one lane per chunk

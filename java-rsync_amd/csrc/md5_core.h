@@ -132,8 +132,14 @@ RSH_HD void md5_compress(Md5State& st, const uint32_t (&m)[16]) {
 // measured against are history in DESIGN.md section 4; only this one is in the tree.  The host pass sees the portable one.
 #if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
 #include "md5_asm.inc"
+#ifdef RSH_KBENCH
+#include "md5_asm_nonop.inc"  // md5_compress_rot16: no s_nop 0 between the steps (kbench variant 1025 only)
+#endif
 #else
 RSH_HD void md5_compress_rot16n(Md5State& st, const uint32_t (&m)[16]) { md5_compress(st, m); }
+#ifdef RSH_KBENCH
+RSH_HD void md5_compress_rot16(Md5State& st, const uint32_t (&m)[16]) { md5_compress(st, m); }
+#endif
 #endif
 
 #if defined(__HIP__)

@@ -44,6 +44,8 @@ enum Opt : int {
     OPT_SUMS_PIECE,        // rsh_sums_*_device / rsh_*_batch_wire: table bytes per pinned staging piece (one launch each)
     OPT_TOKENS_RUNS,       // rsh_receiver_combine_resident: run records per launch of the token walk (a full list: relaunch)
     OPT_K1_DMA,            // 1: the pipelined K1's main waves load straight into LDS at 16-B aligned bases; 0: register staging
+    OPT_K1_PRIO,           // single-file K1 launches of one round: the main waves alternate issue priority (0 off, else
+                           // log2 of the stages per turn; +32: launches of any size too)
     OPT_COUNT
 };
 
@@ -61,6 +63,7 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"chain_map_bytes", 1LL << 30}, {"time_gen", 1},    {"batch_warm", 128},
     {"fault_inject", 0},        {"tokens_span", 256LL << 10}, {"tokens_piece", 8LL << 20},
     {"sums_piece", 32LL << 20}, {"tokens_runs", 64LL << 10}, {"k1_dma", 1},
+    {"k1_prio", 1},
 };
 
 inline const OptInfo* opt_info() { return kOpts; }

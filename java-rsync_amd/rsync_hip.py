@@ -187,7 +187,7 @@ EXPORTS = ["rsh_abi_version", "rsh_strerror", "rsh_last_error", "rsh_device_coun
 DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_reset_options", "rsh_debug_k1_clock",
                  "rsh_debug_streams_busy", "rsh_debug_kernel_ms", "rsh_debug_multi_selftest", "rsh_debug_generation",
                  "rsh_debug_tokens_selftest", "rsh_debug_sums_selftest", "rsh_debug_tokens_scan_selftest",
-                 "rsh_debug_untokens_selftest", "rsh_debug_k1_dma_swizzle"]
+                 "rsh_debug_untokens_selftest", "rsh_debug_k1_dma_swizzle", "rsh_debug_k1_wave_times"]
 
 _LIB = None
 
@@ -286,6 +286,7 @@ def lib():
         "rsh_debug_reset_options": ([], None),
         "rsh_debug_k1_dma_swizzle": ([I32, I32, I32], ctypes.c_int32),
         "rsh_debug_k1_clock": ([P, P, I64, I32, I32, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
+        "rsh_debug_k1_wave_times": ([P, P, I64, I32, I32, P, I64, P, P], ctypes.c_int),
         "rsh_debug_streams_busy": ([P, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
         "rsh_debug_generation": ([P, I32, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
         "rsh_debug_kernel_ms": ([P, I32, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),

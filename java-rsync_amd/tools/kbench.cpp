@@ -10,6 +10,11 @@
 // variant 1010: the pipelined K1 with its weak sums on the VALU (v_dot4) instead of the MFMAs (energy A/B).
 // variant 1020 / 1021: the production abortable launch in the DMA form / the register-staged form (option k1_dma);
 // variant 1022: the two interleaved launch by launch in one process.
+// variant 1100 + k (k = 0..63): the production abortable launch with option k1_prio = k (k >= 32: launches of more
+// than one round too); 1200 + k: k1_prio 0 and k interleaved launch by launch (0 runs the same instructions and sets
+// priority 0 every time, so the pair differs in the priorities alone, not in code placement).
+// variant 1025: the DMA form with the MD5 steps without their s_nop 0 (md5_asm_nonop.inc); 1500 + k: the production
+// launch and 1025 interleaved, both at k1_prio = k.
 // variant 1023 / 1024: the DMA form's diagnostic builds, compute only (a zero-record descriptor drops every load) /
 // loads only (no MD5, no MFMAs); their sums are not the chunks' (parity MISMATCH is expected).
 // (The rejected K1 forms measured in rounds 1-4 -- the coalesced kernel's MD5 step forms, LDS-DMA stages, 4 waves per
@@ -23,6 +28,7 @@
 #include <vector>
 
 #include "device.h"
+#include "options.h"
 #include "token_frame.h"
 #include "token_scan.h"
 
@@ -409,6 +415,10 @@ int main(int argc, char** argv) {
     rsh::K1Tail* d_tails = reinterpret_cast<rsh::K1Tail*>(d_segs + segs.size());
     if (!tails.empty()) CK(hipMemcpy(d_tails, tails.data(), tails.size() * sizeof(rsh::K1Tail), hipMemcpyHostToDevice));
     auto launch = [&](int v) {
+        if (v >= 1100 && v < 1164) {
+            rsh::opt_table()[rsh::OPT_K1_PRIO].store(v - 1100);
+            v = 1000;
+        }
         if (v == 1003)
             return rsh::launch_block_sums_segments(d_segs, (uint32_t)segs.size(), d_tails, (uint32_t)tails.size(),
                                                    (uint32_t)std::count_if(tails.begin(), tails.end(),
@@ -421,7 +431,7 @@ int main(int argc, char** argv) {
             return rsh::launch_block_sums_batch(d_groups, (uint32_t)groups.size(), d_lanes, (uint32_t)lanes.size(),
                                                 lane_align, 0x04030201u, s);
         if (v == 1000) return rsh::launch_block_sums_variant(-1, d, n, B, C, dl, 0x04030201u, w, sx, s, abort_word, 1);
-        if (v == 1010 || (v >= 1020 && v <= 1024 && v != 1022))
+        if (v == 1010 || (v >= 1020 && v <= 1025 && v != 1022))
             return rsh::launch_block_sums_variant(v, d, n, B, C, dl, 0x04030201u, w, sx, s, abort_word, 1);
         if (v == 1001) return rsh::launch_block_sums(d, n, B, C, dl, 0x04030201u, w, sx, s);  // the production entry
         return rsh::launch_block_sums_variant(v, d, n, B, C, dl, 0x04030201u, w, sx, s);
@@ -431,12 +441,14 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e1));
     for (int a = 5; a < argc; ++a) {
         const int v = atoi(argv[a]);
-        if (v == 1022) {  // 1020 and 1021 interleaved, launch by launch: the same clock and HBM state for both forms
+        const bool prio_pair = (v >= 1200 && v < 1264) || (v >= 1500 && v < 1564);
+        if (v == 1022 || prio_pair) {  // 1020 and 1021 interleaved, launch by launch: the same clock and HBM state for both forms
+            const int pair[2] = {v == 1022 ? 1020 : v < 1500 ? 1100 : v - 400, v == 1022 ? 1021 : v < 1500 ? v - 100 : 1025};
             float best[2] = {1e30f, 1e30f}, tot[2] = {0, 0};
             bool same[2];
             for (int f = 0; f < 2; ++f) {
                 CK(hipMemset(w, 0, C * 4));
-                CK(launch(1020 + f));
+                CK(launch(pair[f]));
                 CK(hipStreamSynchronize(s));
                 CK(hipMemcpy(hw.data(), w, C * 4, hipMemcpyDeviceToHost));
                 CK(hipMemcpy(hs.data(), sx, (size_t)C * dl, hipMemcpyDeviceToHost));
@@ -445,7 +457,7 @@ int main(int argc, char** argv) {
             for (int r = 0; r < 2 * reps; ++r) {
                 const int f = r & 1;
                 CK(hipEventRecord(e0, s));
-                CK(launch(1020 + f));
+                CK(launch(pair[f]));
                 CK(hipEventRecord(e1, s));
                 CK(hipEventSynchronize(e1));
                 float ms;
@@ -455,7 +467,7 @@ int main(int argc, char** argv) {
             }
             for (int f = 0; f < 2; ++f)
                 printf("variant %d (interleaved)  n=%lld B=%u C=%u  avg %.3f ms  best %.3f ms  %.1f GB/s  parity=%s\n",
-                       1020 + f, (long long)n, B, C, tot[f] / reps, best[f], n / (tot[f] / reps / 1e3) / 1e9,
+                       pair[f], (long long)n, B, C, tot[f] / reps, best[f], n / (tot[f] / reps / 1e3) / 1e9,
                        same[f] ? "ok" : "MISMATCH");
             fflush(stdout);
             continue;
