@@ -206,6 +206,23 @@ typedef struct {
     int32_t reserved;
 } rsh_token_job;
 int rsh_tokens_write_batch_device(rsh_ctx* ctx, rsh_token_job* jobs, int32_t njobs);
+/* The same segment into device memory: every file's whole stream, trailer included, at d_out (any byte alignment), so
+ * that a segment's Receiver on the same device takes the streams where they lie
+ * (rsh_receiver_combine_batch_resident).  The checks and per-job statuses are those of the form above; the spans of
+ * all files point straight at their d_out and run in one launch, and the trailers of all files are placed by one more. */
+typedef struct {
+    const void* d_src;
+    int64_t n;
+    const rsh_event* ev;   /* host */
+    int64_t n_ev;
+    uint8_t file_md5[16];
+    void* d_out;           /* device, caller-owned: out_cap bytes */
+    int64_t out_cap;
+    int64_t out_len;       /* out: the stream's size */
+    int32_t status;        /* out */
+    int32_t reserved;
+} rsh_token_frame_job;
+int rsh_tokens_frame_batch_device(rsh_ctx* ctx, rsh_token_frame_job* jobs, int32_t njobs);
 
 /* Generator channel bytes: header + per chunk putInt(weak) + digest_length bytes. */
 int64_t rsh_generator_bytes(const rsh_header* h, const int32_t* weak, const uint8_t* strong, uint8_t* out,
@@ -441,6 +458,27 @@ int rsh_receiver_combine_device(rsh_ctx* ctx, const uint8_t* tokens, int64_t tok
 int rsh_receiver_combine_resident(rsh_ctx* ctx, const void* d_tokens, int64_t tokens_len, const rsh_header* h,
                                   const void* d_replica, int64_t replica_len, int32_t defer_write, void* d_target,
                                   int64_t target_cap, int32_t flags, rsh_combine_result* out);
+/* A segment of such files in one call: one job per file, every pointer a device pointer.  Each job gets exactly what
+ * rsh_receiver_combine_resident gives for the same arguments -- result, status, target bytes; a failed file's target
+ * is untouched.  The files' walks share launches (token_scan_batch_kernel, a workgroup per file; a file whose run list
+ * of option tokens_runs_batch records was full walks on in the next round), every file's ranges are one gather launch
+ * and every file's literal runs one unframe launch.  Unless flags has RSH_COMBINE_NO_MD5 the result bytes then come
+ * to the host, as many files at a time as option resident_md5_bytes of pinned staging holds, and are digested side by
+ * side on the host's cores.  Returns RSH_OK or the first failing job's status in file order; a call that fails as a
+ * whole (RSH_E_DEVICE) leaves every file it did not finish with its code.  njobs == 0 launches nothing. */
+typedef struct {
+    const void* d_tokens;     /* the file's token stream, ending with putInt(0) */
+    int64_t tokens_len;
+    rsh_header h;
+    const void* d_replica;    /* NULL: none */
+    int64_t replica_len;
+    int32_t defer_write;
+    int32_t status;           /* out */
+    void* d_target;           /* target_cap bytes (nothing written when intact) */
+    int64_t target_cap;
+    rsh_combine_result res;   /* out */
+} rsh_resident_job;
+int rsh_receiver_combine_batch_resident(rsh_ctx* ctx, rsh_resident_job* jobs, int32_t njobs, int32_t flags);
 
 /* ---- a segment's Receiver from host memory (Receiver.receiveFiles, Receiver.java:1145-1263: combineDataToFile
  * :459-556 and isRemoteAndLocalFileIdentical :824-842 for each file in turn) ----

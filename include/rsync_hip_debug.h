@@ -7,7 +7,7 @@
  * Tests force rare paths with them; a few are tunables: k1_gather, k1_shift,
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
- * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio.
+ * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio, tokens_runs_batch, resident_md5_bytes.
  *
  * k1_dma = 1 (default): the main waves of the pipelined K1 stream their stages from HBM straight into LDS wherever
  * every wave's base is 16-B aligned; 0: the register-staged form at every base (the A/B partner, from one library).
@@ -121,6 +121,26 @@ typedef struct {
 } rsh_token_run;
 int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
                                    rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status);
+
+/* The segment's walk, token_scan_batch_kernel: one pass over the files live[0, nlive) (distinct indices into jobs), each
+ * from its own `from` into its own `runs` (cap records, 1 .. 2^24), a workgroup per file.  ctx == NULL: tokens and runs
+ * are host memory and the host stand-in runs a round of `lanes` lanes (a multiple of 64 up to 1024; 0: the kernel's
+ * width) -- 64 is the single-file walk's round.  Otherwise they are device memory and the kernel runs, all files in one
+ * launch (lanes 0 or the kernel's width).  n_runs, pos and status as rsh_debug_tokens_scan_selftest's; a file that is
+ * not in `live` gets -1 in all three (on the device: the bytes its entry held before the launch). */
+typedef struct {
+    const uint8_t* tokens;
+    int64_t tokens_len;
+    int64_t from;
+    rsh_token_run* runs;
+    int64_t cap;
+    int64_t n_runs;   /* out */
+    int64_t pos;      /* out */
+    int32_t status;   /* out */
+    int32_t reserved;
+} rsh_token_scan_job;
+int rsh_debug_tokens_scan_batch_selftest(rsh_ctx* ctx, rsh_token_scan_job* jobs, int32_t njobs, const int32_t* live,
+                                         int32_t nlive, int32_t lanes);
 
 /* token_unframe_kernel on one literal run: `count` >= 2 tokens of T >= 16 bytes whose first header is at stream offset
  * pos (else RSH_E_INVAL), their data placed at out[0, count * T) in spans of `span` bytes (0: option tokens_span).

@@ -204,10 +204,10 @@ int rsh_ctx_trim(rsh_ctx* ctx) {
     RSH_HIP(hipSetDevice(ctx->device));
     for (hipStream_t st : {ctx->stream, ctx->aux, ctx->phase}) RSH_HIP(hipStreamSynchronize(st));
     for (DevBuf* b : {&ctx->data, &ctx->weak, &ctx->strong, &ctx->seg_data, &ctx->seg_tab, &ctx->rcv[0], &ctx->rcv[1],
-                      &ctx->rcv_ops[0], &ctx->rcv_ops[1], &ctx->out, &ctx->sums_raw})
+                      &ctx->rcv_ops[0], &ctx->rcv_ops[1], &ctx->out, &ctx->sums_raw, &ctx->tokb_runs, &ctx->tokb_outs})
         b->release();
     for (PinnedBuf* b : {&ctx->h_stage, &ctx->h_rcv_ops[0], &ctx->h_rcv_ops[1], &ctx->h_out, &ctx->h_tok, &ctx->h_tokd[0],
-                         &ctx->h_tokd[1], &ctx->h_sums, &ctx->h_sumsd})
+                         &ctx->h_tokd[1], &ctx->h_sums, &ctx->h_sumsd, &ctx->h_tokb, &ctx->h_tokb_runs, &ctx->h_rmd5})
         b->release();
     if (ctx->h_win.cap > (1u << 20)) ctx->h_win.release();  // (a Receiver pass's pieces; the scan's windows are small)
     // The batched scan's state stays: its chunk index, hit map, descriptors, pinned event and

@@ -279,6 +279,10 @@ struct rsh_ctx {
     // span descriptors (receiver.cpp)
     DevBuf tok_runs;
     PinnedBuf h_runs, h_untok;
+    // rsh_receiver_combine_batch_resident: every file's run list and TokScanOut in HBM, the pinned descriptors of the
+    // segment's walk (with the outs' host copy), the records' host copy, and the staging of the verify digests' bytes
+    DevBuf tokb_runs, tokb_outs;
+    PinnedBuf h_tokb, h_tokb_runs, h_rmd5;
     hipEvent_t ev_sums_a = nullptr, ev_sums_b = nullptr;  // timing: the last sums kernel (rsh_debug_kernel_ms)
     bool sums_timed = false;
     std::atomic<bool> busy{false};   // the staging buffers and last_ev serve one call at a time
@@ -288,12 +292,12 @@ struct rsh_ctx {
         for (DevBuf* b : {&data, &weak, &strong, &src_weak, &src_strong, &flags, &ph_weak[0], &ph_strong[0],
                           &ph_weak[1], &ph_strong[1], &slots, &dslots,
                           &out, &first, &haw, &partials, &bucket, &seg_data, &seg_tab,
-                          &rcv[0], &rcv[1], &rcv_ops[0], &rcv_ops[1], &prep_dev, &fc_dev, &sums_raw, &tok_runs})
+                          &rcv[0], &rcv[1], &rcv_ops[0], &rcv_ops[1], &prep_dev, &fc_dev, &sums_raw, &tok_runs, &tokb_runs, &tokb_outs})
             b->release();
         for (PinnedBuf* b : {&h_weak, &h_strong, &h_aw, &h_as, &h_fl, &h_pw[0], &h_ps[0], &h_pw[1], &h_ps[1], &h_lead, &h_pos, &h_out, &h_iv,
                              &h_tiles, &h_keys, &h_first, &h_win, &h_ptiles, &h_psegs, &h_hit, &h_win0, &h_pend, &h_bucket, &h_files,
                              &h_stage, &h_rcv_ops[0], &h_rcv_ops[1], &h_prep, &h_stamps, &h_fgw, &h_fjobs, &h_fout,
-                             &h_tok, &h_tokd[0], &h_tokd[1], &h_sums, &h_sumsd, &h_runs, &h_untok})
+                             &h_tok, &h_tokd[0], &h_tokd[1], &h_sums, &h_sumsd, &h_runs, &h_untok, &h_tokb, &h_tokb_runs, &h_rmd5})
             b->release();
         if (abort_word) (void)hipFree(abort_word);
         if (ev_in) (void)hipEventDestroy(ev_in);

@@ -4,7 +4,8 @@
 // token_scan_kernel and token_unframe_kernel: the Receiver's side of a stream that lies in HBM -- the token walk as a
 // run list, one wave proving up to 64 literal or 1024 match tokens per memory round trip, and the literal runs placed
 // from the raw stream, the framer's mirror on the framer's grid (token_scan.h; receiver.cpp plans and owns the entry
-// points).
+// points).  token_scan_batch_kernel: the walk of a segment's files in one launch, a workgroup per file and several
+// waves to a round.
 #include <hip/hip_runtime.h>
 
 #include "device.h"
@@ -204,6 +205,72 @@ hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, T
     hipLaunchKernelGGL(token_scan_kernel, dim3(1), dim3(kScanLanes), 0, s, tokens, len, from, runs, cap, out);
     return hipGetLastError();
 }
+
+// A segment's walk: workgroup b walks file live[b] from its descriptor's `from`, W waves to a round.  Each wave finds
+// its leading full lanes and its first other lane's count as token_scan_kernel does; the pairs meet in LDS and every
+// thread adds them up the same way (tok_scan_combine), so that the walk's control flow stays uniform over the
+// workgroup: head(pos) reads one address in every lane, and a round's result comes out of LDS.  A round writes the
+// pair buffer the round before it did not, so one barrier per round is enough: a wave can only be two rounds ahead
+// of another after that one has passed the barrier between them.  Thread 0 stores the records and the TokScanOut.
+template <uint32_t W>
+__global__ __launch_bounds__(kScanLanes * W) void token_scan_batch_kernel(const TokScanJob* __restrict__ jobs,
+                                                                         const int32_t* __restrict__ live,
+                                                                         TokScanOut* __restrict__ outs) {
+    typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
+    typedef TokRun __attribute__((address_space(1))) * GlobalRuns;
+    __shared__ uint32_t s_full[2][W], s_part[2][W];
+    const int32_t job = live[blockIdx.x];
+    const TokScanJob J = jobs[job];
+    const GlobalByte base = (GlobalByte)(uintptr_t)J.tokens;
+    // (the records' address comes out of memory: through the global address space, so that the stores are not flat_)
+    TokRun* const runs = (TokRun*)(GlobalRuns)(uintptr_t)J.runs;
+    const int64_t len = J.len;
+    const uint32_t tid = threadIdx.x, lane = tid % kScanLanes, wave = tid / kScanLanes;
+    uint32_t turn = 0;
+    auto ld = [&](int64_t off) -> int32_t {
+        const GlobalByte p = base + off;
+        return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+    };
+    auto head = [&](int64_t pos) -> int32_t { return __builtin_amdgcn_readfirstlane(ld(pos)); };
+    auto round = [&](int64_t pos, int32_t v) -> int64_t {
+        const uint32_t per = v > 0 ? 1u : kScanMatchPer;
+        const uint32_t c = tok_scan_lane(ld, pos, len, v, tid);
+        const unsigned long long full = __ballot(c == per);
+        const uint32_t L = full == ~0ull ? kScanLanes : (uint32_t)__builtin_ctzll(~full);
+        const uint32_t part = L < kScanLanes ? (uint32_t)__shfl((int)c, (int)L) : 0u;
+        if (lane == 0) {
+            s_full[turn][wave] = L;
+            s_part[turn][wave] = part;
+        }
+        __syncthreads();
+        const int64_t m = tok_scan_combine(s_full[turn], s_part[turn], W, per);
+        turn ^= 1u;
+        return m;
+    };
+    tok_scan_walk(head, round, len, J.from, runs, J.cap, tid == 0, outs + job);
+}
+
+hipError_t launch_token_scan_batch(const TokScanJob* jobs, const int32_t* live, uint32_t nlive, TokScanOut* outs,
+                                   hipStream_t s) {
+    if (nlive == 0) return hipSuccess;
+    hipLaunchKernelGGL(token_scan_batch_kernel<kScanBatchWaves>, dim3(nlive), dim3(kScanLanes * kScanBatchWaves), 0, s,
+                       jobs, live, outs);
+    return hipGetLastError();
+}
+#ifdef RSH_KBENCH
+hipError_t launch_token_scan_batch_variant(uint32_t waves, const TokScanJob* jobs, const int32_t* live, uint32_t nlive,
+                                           TokScanOut* outs, hipStream_t s) {
+    const dim3 g(nlive), b(kScanLanes * waves);
+    switch (waves) {
+        case 1: hipLaunchKernelGGL(token_scan_batch_kernel<1>, g, b, 0, s, jobs, live, outs); break;
+        case 4: hipLaunchKernelGGL(token_scan_batch_kernel<4>, g, b, 0, s, jobs, live, outs); break;
+        case 8: hipLaunchKernelGGL(token_scan_batch_kernel<8>, g, b, 0, s, jobs, live, outs); break;
+        case 16: hipLaunchKernelGGL(token_scan_batch_kernel<16>, g, b, 0, s, jobs, live, outs); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+#endif
 
 // This file's code object, loaded by rsh_ctx_create (as warm_io_kernel for device_io.hip).
 __global__ void warm_tokens_kernel() {}

@@ -46,6 +46,8 @@ enum Opt : int {
     OPT_K1_DMA,            // 1: the pipelined K1's main waves load straight into LDS at 16-B aligned bases; 0: register staging
     OPT_K1_PRIO,           // single-file K1 launches of one round: the main waves alternate issue priority (0 off, else
                            // log2 of the stages per turn; +32: launches of any size too)
+    OPT_TOKENS_RUNS_BATCH, // rsh_receiver_combine_batch_resident: run records per file and launch of the segment's token walk
+    OPT_RESIDENT_MD5_BYTES,  // ... pinned staging of the verify digests' downloads (a larger file is digested piece by piece)
     OPT_COUNT
 };
 
@@ -63,7 +65,7 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"chain_map_bytes", 1LL << 30}, {"time_gen", 1},    {"batch_warm", 128},
     {"fault_inject", 0},        {"tokens_span", 256LL << 10}, {"tokens_piece", 8LL << 20},
     {"sums_piece", 32LL << 20}, {"tokens_runs", 64LL << 10}, {"k1_dma", 1},
-    {"k1_prio", 1},
+    {"k1_prio", 1},             {"tokens_runs_batch", 4096}, {"resident_md5_bytes", 1LL << 30},
 };
 
 inline const OptInfo* opt_info() { return kOpts; }

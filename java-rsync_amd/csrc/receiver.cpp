@@ -8,7 +8,8 @@
 // it runs on the host while the next piece of the file comes back over PCIe.
 //
 // rsh_receiver_combine_resident takes the stream itself from HBM: there the walk runs on the device and the host
-// plans runs of tokens (the second half of this file).
+// plans runs of tokens (the second half of this file); rsh_receiver_combine_batch_resident does so for a segment's
+// files at once, their walks, gathers and unframing sharing the launches.
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -544,18 +545,29 @@ int64_t untok_span_bytes(int64_t forced = 0) {
     return std::min<int64_t>(std::max<int64_t>(forced > 0 ? forced : opt(OPT_TOKENS_SPAN), 16), kTokMaxSpan);
 }
 
-// The walk over host pointers: token_scan_kernel's lanes one after another.
-void scan_host(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out) {
+// The walk over host pointers: the kernels' lanes one after another, `lanes` of them to a round (64: token_scan_kernel;
+// 64 W: token_scan_batch_kernel's W waves, each wave's pair found as the kernel's ballot finds it and the pairs added
+// up by the kernel's tok_scan_combine).
+void scan_host(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
+               uint32_t lanes = kScanLanes) {
     auto ld = [&](int64_t off) { return get_int(tokens + off); };
+    const uint32_t waves = lanes / kScanLanes;
     auto round = [&](int64_t pos, int32_t v) -> int64_t {
         const uint32_t per = v > 0 ? 1u : kScanMatchPer;
-        int64_t m = 0;
-        for (uint32_t lane = 0; lane < kScanLanes; ++lane) {
-            const uint32_t c = tok_scan_lane(ld, pos, len, v, lane);
-            m += c;
-            if (c != per) break;
+        uint32_t full[kScanMaxWaves], part[kScanMaxWaves];
+        for (uint32_t w = 0; w < waves; ++w) {
+            full[w] = kScanLanes;
+            part[w] = 0;
+            for (uint32_t i = 0; i < kScanLanes; ++i) {
+                const uint32_t c = tok_scan_lane(ld, pos, len, v, kScanLanes * w + i);
+                if (c != per) {
+                    full[w] = i;
+                    part[w] = c;
+                    break;
+                }
+            }
         }
-        return m;
+        return tok_scan_combine(full, part, waves, per);
     };
     tok_scan_walk(ld, round, len, from, runs, cap, true, out);
 }
@@ -624,10 +636,8 @@ int scan_device_runs(rsh_ctx* c, const uint8_t* d_tokens, int64_t len, int64_t f
 
 // The launches of a resident plan: replica ranges and the literal runs the unframe kernel does not take as gather ops,
 // the other literal runs as unframe spans.
-int place_resident(rsh_ctx* c, const RunPlan& P, const uint8_t* d_tokens, const uint8_t* d_replica, uint8_t* d_target) {
-    std::vector<GatherOp> ops;
-    std::vector<UntokSpan> spans;
-    const int64_t span = untok_span_bytes();
+void plan_resident(const RunPlan& P, const uint8_t* d_tokens, const uint8_t* d_replica, uint8_t* d_target, int64_t span,
+                   std::vector<GatherOp>& ops, std::vector<UntokSpan>& spans) {  // (appends: a segment's files share them)
     int64_t t = 0;
     auto range = [&](const uint8_t* src, uint8_t* dst, int64_t len) {
         for (int64_t o = 0; o < len; o += kOpPiece) ops.push_back(GatherOp{src + o, dst + o, std::min<int64_t>(kOpPiece, len - o)});
@@ -639,6 +649,8 @@ int place_resident(rsh_ctx* c, const RunPlan& P, const uint8_t* d_tokens, const 
             for (int64_t k = 0; k < p.count; ++k) range(d_tokens + p.off + k * ((int64_t)p.T + 4) + 4, d_target + t + k * p.T, p.T);
         t += p.len;
     }
+}
+int launch_resident(rsh_ctx* c, const std::vector<GatherOp>& ops, const std::vector<UntokSpan>& spans) {
     if (ops.size() > (size_t)INT32_MAX || spans.size() > (size_t)INT32_MAX) return RSH_E_INVAL;
     if (!ops.empty()) {
         RSH_HIP(c->h_pos.ensure(ops.size() * sizeof(GatherOp)));  // read by the kernel from pinned memory
@@ -654,6 +666,243 @@ int place_resident(rsh_ctx* c, const RunPlan& P, const uint8_t* d_tokens, const 
         for (const UntokSpan& s : spans) max_len = std::max(max_len, s.len);
         RSH_HIP(launch_token_unframe(c->h_untok.as<UntokSpan>(), (uint32_t)spans.size(), max_len, c->stream));
     }
+    return RSH_OK;
+}
+int place_resident(rsh_ctx* c, const RunPlan& P, const uint8_t* d_tokens, const uint8_t* d_replica, uint8_t* d_target) {
+    std::vector<GatherOp> ops;
+    std::vector<UntokSpan> spans;
+    plan_resident(P, d_tokens, d_replica, d_target, untok_span_bytes(), ops, spans);
+    return launch_resident(c, ops, spans);
+}
+
+// ------------------------------------------------------------------------------------------------
+// A segment's Receiver over streams in HBM (rsh_receiver_combine_batch_resident): token_scan_batch_kernel walks every
+// file still walking in one launch, a workgroup per file; one download brings the TokScanOuts down and one copy launch
+// the records in use; the host runs each file's RunPlan over its records; files whose list was full go into the next
+// round.  A round is two launches, one copy and two synchronisations whatever the file count.  Then every surviving
+// file's ranges are one gather launch and every file's literal runs one unframe launch.
+// ------------------------------------------------------------------------------------------------
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// The pinned block of a segment's walk (c->h_tokb): the descriptors, the TokScanOuts' host copy, the list of the files
+// still walking and the record copies' entries, for n files.
+struct WalkBlock {
+    TokScanJob* jobs;
+    TokScanOut* outs;
+    int32_t* live;
+    CopyEnt* ents;
+    static size_t bytes(size_t n) {
+        return align16(n * sizeof(TokScanJob)) + align16(n * sizeof(TokScanOut)) + align16(n * sizeof(int32_t)) +
+               align16(n * sizeof(CopyEnt));
+    }
+    WalkBlock(uint8_t* p, size_t n) {
+        jobs = reinterpret_cast<TokScanJob*>(p);
+        p += align16(n * sizeof(TokScanJob));
+        outs = reinterpret_cast<TokScanOut*>(p);
+        p += align16(n * sizeof(TokScanOut));
+        live = reinterpret_cast<int32_t*>(p);
+        p += align16(n * sizeof(int32_t));
+        ents = reinterpret_cast<CopyEnt*>(p);
+    }
+};
+
+// One launch of the segment's walk over the files live[0, nlive) of W.jobs[0, n), and the download of every file's
+// TokScanOut into W.outs (a file that did not walk keeps what `fill` left in its entry: 0xFF from the debug entry).
+int walk_round(rsh_ctx* c, const WalkBlock& W, size_t n, uint32_t nlive, bool fill) {
+    RSH_HIP(c->tokb_outs.ensure(n * sizeof(TokScanOut)));
+    TokScanOut* d_outs = c->tokb_outs.as<TokScanOut>();
+    if (fill) RSH_HIP(hipMemsetAsync(d_outs, 0xFF, n * sizeof(TokScanOut), c->stream));
+    RSH_HIP(launch_token_scan_batch(W.jobs, W.live, nlive, d_outs, c->stream));
+    RSH_HIP(hipMemcpyAsync(W.outs, d_outs, n * sizeof(TokScanOut), hipMemcpyDeviceToHost, c->stream));
+    RSH_HIP(hipStreamSynchronize(c->stream));
+    return RSH_OK;
+}
+
+// One file of the segment while the call runs.
+struct ResFile {
+    int32_t job;
+    RunPlan plan;
+    ResFile(int32_t j, const rsh_resident_job& r)
+        : job(j), plan(r.h, r.d_replica != nullptr, r.replica_len, r.defer_write != 0) {}
+};
+
+// The walk rounds of files[0, n): on return every file's plan is complete and end[k] the byte after its putInt(0), or
+// jobs[files[k].job].status holds its error.  Returns other than RSH_OK for a failure of the call as a whole.
+int walk_files(rsh_ctx* c, rsh_resident_job* jobs, std::vector<std::unique_ptr<ResFile>>& files, std::vector<int64_t>& end) {
+    const size_t n = files.size();
+    const int64_t cap = std::min<int64_t>(std::max<int64_t>(opt(OPT_TOKENS_RUNS_BATCH), 1), 1 << 24);
+    const size_t stride = align16((size_t)cap * sizeof(TokRun));  // (the copy kernel's destinations are 16-byte aligned)
+    RSH_HIP(c->tokb_runs.ensure(n * stride));
+    RSH_HIP(c->h_tokb_runs.ensure(n * stride));
+    RSH_HIP(c->h_tokb.ensure(WalkBlock::bytes(n)));
+    const WalkBlock W(c->h_tokb.as<uint8_t>(), n);
+    uint8_t* const d_runs = c->tokb_runs.as<uint8_t>();
+    const uint8_t* const h_runs = c->h_tokb_runs.as<uint8_t>();
+    std::vector<int32_t> live;
+    for (size_t k = 0; k < n; ++k) {
+        const rsh_resident_job& j = jobs[files[k]->job];
+        W.jobs[k] = TokScanJob{static_cast<const uint8_t*>(j.d_tokens), j.tokens_len, 0,
+                               reinterpret_cast<TokRun*>(d_runs + k * stride), cap};
+        live.push_back((int32_t)k);
+    }
+    while (!live.empty()) {
+        memcpy(W.live, live.data(), live.size() * sizeof(int32_t));
+        const int rc = walk_round(c, W, n, (uint32_t)live.size(), false);
+        if (rc != RSH_OK) return rc;
+        uint32_t nent = 0;
+        int64_t max_len = 0;
+        for (const int32_t k : live) {
+            const TokScanOut& so = W.outs[k];
+            if (so.n < 0 || so.n > cap || (so.status == TOK_SCAN_MORE && so.pos <= W.jobs[k].from)) return RSH_E_DEVICE;
+            if (so.n == 0) continue;
+            const int64_t bytes = so.n * (int64_t)sizeof(TokRun);
+            W.ents[nent++] = CopyEnt{d_runs + (size_t)k * stride, const_cast<uint8_t*>(h_runs) + (size_t)k * stride, bytes};
+            max_len = std::max(max_len, bytes);
+        }
+        RSH_HIP(launch_copy_many(W.ents, nent, max_len, c->stream));
+        RSH_HIP(hipStreamSynchronize(c->stream));
+        std::vector<int32_t> next;
+        for (const int32_t k : live) {
+            const TokScanOut& so = W.outs[k];
+            const TokRun* runs = reinterpret_cast<const TokRun*>(h_runs + (size_t)k * stride);
+            int rp = RSH_OK;
+            for (int64_t i = 0; i < so.n && rp == RSH_OK; ++i) rp = files[(size_t)k]->plan.add(runs[i]);
+            // (cut short: after every token before the cut was planned)
+            if (rp == RSH_OK && so.status != TOK_SCAN_MORE && so.status != TOK_SCAN_END) rp = RSH_E_INVAL;
+            if (rp != RSH_OK) {
+                jobs[files[(size_t)k]->job].status = rp;
+            } else if (so.status == TOK_SCAN_MORE) {
+                W.jobs[k].from = so.pos;
+                next.push_back(k);
+            } else {
+                end[(size_t)k] = so.pos;
+            }
+        }
+        live.swap(next);
+    }
+    return RSH_OK;
+}
+
+// The verify digests of a segment's resident files: each file's result bytes come to pinned staging, as many files at
+// a time as option resident_md5_bytes holds, and are digested side by side (md5_files); a file larger than the staging
+// goes through md5_device piece by piece.  Every byte crosses PCIe once: this leg runs at the link's rate.
+struct Md5Src {
+    int32_t job;
+    const uint8_t* d;
+    int64_t len;
+};
+int digest_resident(rsh_ctx* c, rsh_resident_job* jobs, const std::vector<Md5Src>& srcs) {
+    const int64_t budget = std::max<int64_t>(opt(OPT_RESIDENT_MD5_BYTES), 64);
+    std::vector<std::pair<size_t, size_t>> groups;  // [first, last) of the files that fit the staging
+    int64_t most = 0;
+    {
+        size_t a = 0;
+        int64_t used = 0;
+        for (size_t i = 0; i < srcs.size(); ++i) {
+            const int64_t b = (int64_t)alignr(srcs[i].len);
+            if (b > budget) {  // digested on its own below
+                if (i > a) groups.emplace_back(a, i);
+                a = i + 1;
+                used = 0;
+                continue;
+            }
+            if (i > a && used + b > budget) {
+                groups.emplace_back(a, i);
+                a = i;
+                used = 0;
+            }
+            used += b;
+            most = std::max(most, used);
+        }
+        if (srcs.size() > a) groups.emplace_back(a, srcs.size());
+    }
+    if (most > 0) RSH_HIP(c->h_rmd5.ensure((size_t)most));
+    uint8_t* const stage = c->h_rmd5.as<uint8_t>();
+    std::vector<rsh_piece> pieces;
+    std::vector<Md5File> in;
+    std::vector<uint8_t> out;
+    for (const auto& g : groups) {
+        pieces.clear();
+        in.clear();
+        int64_t at = 0;
+        for (size_t i = g.first; i < g.second; ++i) {
+            if (srcs[i].len > 0)
+                RSH_HIP(hipMemcpyAsync(stage + at, srcs[i].d, (size_t)srcs[i].len, hipMemcpyDeviceToHost, c->stream));
+            pieces.push_back(rsh_piece{stage + at, srcs[i].len});
+            at += alignr(srcs[i].len);
+        }
+        for (size_t i = 0; i < pieces.size(); ++i) in.push_back(Md5File{&pieces[i], pieces[i].len > 0 ? 1 : 0});
+        RSH_HIP(hipStreamSynchronize(c->stream));
+        out.assign(in.size() * 16 + 16, 0);
+        md5_files(in.data(), (int32_t)in.size(), reinterpret_cast<uint8_t(*)[16]>(out.data()), call_cores(),
+                  (int)opt(OPT_MD5_WIDTH));
+        for (size_t i = g.first; i < g.second; ++i) memcpy(jobs[srcs[i].job].res.md5, out.data() + 16 * (i - g.first), 16);
+    }
+    for (const Md5Src& s : srcs) {
+        if ((int64_t)alignr(s.len) <= budget) continue;
+        const int rc = md5_device(c, s.d, s.len, jobs[s.job].res.md5);
+        if (rc != RSH_OK) return rc;
+    }
+    return RSH_OK;
+}
+
+// The call with the context claimed: fin[i] = 1 once job i's status and result are final.
+int combine_batch_resident(rsh_ctx* c, rsh_resident_job* jobs, int32_t njobs, int32_t flags, std::vector<char>& fin) {
+    std::vector<std::unique_ptr<ResFile>> files;
+    for (int32_t i = 0; i < njobs; ++i) {
+        rsh_resident_job& j = jobs[i];
+        j.status = RSH_OK;
+        j.res = rsh_combine_result{};
+        if (!j.d_tokens || j.tokens_len < 0 || j.replica_len < 0 || j.target_cap < 0) {
+            j.status = RSH_E_INVAL;
+            fin[(size_t)i] = 1;
+            continue;
+        }
+        files.emplace_back(new ResFile(i, j));
+    }
+    if (files.empty()) return RSH_OK;
+    // the walk and the plans: every run is validated before anything reads through it
+    std::vector<int64_t> end(files.size(), 0);
+    const int rw = walk_files(c, jobs, files, end);
+    if (rw != RSH_OK) return rw;
+    std::vector<GatherOp> ops;
+    std::vector<UntokSpan> spans;
+    std::vector<Md5Src> srcs;
+    std::vector<int32_t> placed;
+    const int64_t span = untok_span_bytes();
+    for (size_t k = 0; k < files.size(); ++k) {
+        RunPlan& P = files[k]->plan;
+        rsh_resident_job& j = jobs[files[k]->job];
+        if (j.status == RSH_OK) j.status = P.finish();
+        if (j.status != RSH_OK) {
+            fin[(size_t)files[k]->job] = 1;
+            continue;
+        }
+        j.res.tokens_used = end[k];
+        j.res.target_len = P.intact ? 0 : P.target_len;
+        j.res.literal = P.literal;
+        j.res.matched = P.matched;
+        j.res.intact = P.intact ? 1 : 0;
+        if (!P.intact && P.target_len > j.target_cap) j.status = RSH_E_NOSPACE;
+        else if (!P.intact && P.target_len > 0 && !j.d_target) j.status = RSH_E_INVAL;
+        if (j.status != RSH_OK) {
+            fin[(size_t)files[k]->job] = 1;
+            continue;
+        }
+        const uint8_t* rep = static_cast<const uint8_t*>(j.d_replica);
+        uint8_t* tgt = static_cast<uint8_t*>(j.d_target);
+        if (!P.intact) plan_resident(P, static_cast<const uint8_t*>(j.d_tokens), rep, tgt, span, ops, spans);
+        srcs.push_back(Md5Src{files[k]->job, P.intact ? rep : tgt, P.intact ? P.intact_len : P.target_len});
+        placed.push_back(files[k]->job);
+    }
+    const int g = launch_resident(c, ops, spans);
+    if (g != RSH_OK) return g;
+    if (!(flags & RSH_COMBINE_NO_MD5)) {
+        const int d = digest_resident(c, jobs, srcs);
+        if (d != RSH_OK) return d;
+    }
+    RSH_HIP(hipStreamSynchronize(c->stream));  // the descriptors are read until the launches are done
+    for (const int32_t i : placed) fin[(size_t)i] = 1;
     return RSH_OK;
 }
 
@@ -710,6 +959,69 @@ int rsh_receiver_combine_resident(rsh_ctx* ctx, const void* d_tokens, int64_t to
         return RSH_OK;
     }
     return md5_device(ctx, P.intact ? rep : tgt, P.intact ? P.intact_len : P.target_len, out->md5);
+}
+
+int rsh_receiver_combine_batch_resident(rsh_ctx* ctx, rsh_resident_job* jobs, int32_t njobs, int32_t flags) {
+    if (!ctx || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
+    if (njobs == 0) return RSH_OK;
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    std::vector<char> fin((size_t)njobs, 0);
+    const int rc = combine_batch_resident(ctx, jobs, njobs, flags, fin);
+    if (rc != RSH_OK) {
+        (void)hipStreamSynchronize(ctx->stream);  // nothing reads the descriptors after the call
+        for (int32_t i = 0; i < njobs; ++i)
+            if (!fin[(size_t)i] && jobs[i].status == RSH_OK) jobs[i].status = rc;
+        return rc;
+    }
+    for (int32_t i = 0; i < njobs; ++i)
+        if (jobs[i].status != RSH_OK) return jobs[i].status;
+    return RSH_OK;
+}
+
+int rsh_debug_tokens_scan_batch_selftest(rsh_ctx* ctx, rsh_token_scan_job* jobs, int32_t njobs, const int32_t* live,
+                                         int32_t nlive, int32_t lanes) {
+    static_assert(sizeof(rsh_token_scan_job) == 64 && sizeof(rsh_resident_job) == 128, "job layouts (rsync_hip.py)");
+    if (!jobs || njobs < 1 || njobs > (1 << 16) || nlive < 0 || nlive > njobs || (nlive > 0 && !live)) return RSH_E_INVAL;
+    if (lanes == 0) lanes = (int32_t)(kScanLanes * kScanBatchWaves);
+    if (lanes < (int32_t)kScanLanes || lanes % (int32_t)kScanLanes || lanes > (int32_t)(kScanLanes * kScanMaxWaves)) return RSH_E_INVAL;
+    if (ctx && lanes != (int32_t)(kScanLanes * kScanBatchWaves)) return RSH_E_INVAL;  // the kernel has one width
+    std::vector<char> walks((size_t)njobs, 0);
+    for (int32_t i = 0; i < njobs; ++i) {
+        const rsh_token_scan_job& j = jobs[i];
+        if (!j.tokens || j.tokens_len < 0 || j.from < 0 || j.from > j.tokens_len || j.cap < 1 || j.cap > (1 << 24) || !j.runs)
+            return RSH_E_INVAL;
+    }
+    for (int32_t b = 0; b < nlive; ++b) {  // two workgroups must not write one file's records
+        if (live[b] < 0 || live[b] >= njobs || walks[(size_t)live[b]]) return RSH_E_INVAL;
+        walks[(size_t)live[b]] = 1;
+    }
+    std::vector<TokScanOut> outs((size_t)njobs, TokScanOut{-1, -1, -1, -1});
+    if (ctx) {
+        RSH_CLAIM(ctx);
+        RSH_HIP(hipSetDevice(ctx->device));
+        RSH_HIP(ctx->h_tokb.ensure(WalkBlock::bytes((size_t)njobs)));
+        const WalkBlock W(ctx->h_tokb.as<uint8_t>(), (size_t)njobs);
+        for (int32_t i = 0; i < njobs; ++i)
+            W.jobs[i] = TokScanJob{jobs[i].tokens, jobs[i].tokens_len, jobs[i].from, reinterpret_cast<TokRun*>(jobs[i].runs),
+                                   jobs[i].cap};
+        if (nlive > 0) memcpy(W.live, live, (size_t)nlive * sizeof(int32_t));
+        const int rc = walk_round(ctx, W, (size_t)njobs, (uint32_t)nlive, true);
+        if (rc != RSH_OK) return rc;
+        memcpy(outs.data(), W.outs, (size_t)njobs * sizeof(TokScanOut));
+    } else {
+        for (int32_t b = 0; b < nlive; ++b) {
+            const rsh_token_scan_job& j = jobs[live[b]];
+            scan_host(j.tokens, j.tokens_len, j.from, reinterpret_cast<TokRun*>(j.runs), j.cap, &outs[(size_t)live[b]],
+                      (uint32_t)lanes);
+        }
+    }
+    for (int32_t i = 0; i < njobs; ++i) {
+        jobs[i].n_runs = outs[(size_t)i].n;
+        jobs[i].pos = outs[(size_t)i].pos;
+        jobs[i].status = outs[(size_t)i].status;
+    }
+    return RSH_OK;
 }
 
 int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,

@@ -9,6 +9,7 @@
 //          lanes whose int equals v are a run of equal-length tokens (the lanes before a lane prove its position);
 //   v < 0: lane i reads the ints pos + 4 (16 i + j), j < 16; the run is the leading ints that are negative and equal
 //          v - (16 i + j): consecutive block indices.
+// token_scan_batch_kernel walks a segment's files, one workgroup each, with a round several waves wide.
 // A run record holds the stream offset of its first header, the kind, the token length or first block index, and the
 // token count; rounds that continue the last record extend it.  No byte outside [tokens, tokens + len) is read: headers
 // lie at any byte offset, so an int is read as its own four bytes (the compiler makes them one unaligned dword load),
@@ -112,6 +113,36 @@ RSH_HD void tok_scan_walk(const Head& head, const Round& round, int64_t len, int
         pos += v > 0 ? m * ((int64_t)v + 4) : 4 * m;
     }
     if (writer) *out = TokScanOut{pos, n, status, 0};
+}
+
+// ---- the segment's walk ----
+
+// One file of token_scan_batch_kernel's launch (pinned host memory): the walk resumes at `from` and writes at most cap
+// records to `runs` (device memory).  The kernel's grid is the list of the files still walking; a file's TokScanOut is
+// its entry of a device array indexed as the descriptors are.
+struct TokScanJob {
+    const uint8_t* tokens;
+    int64_t len;
+    int64_t from;
+    TokRun* runs;
+    int64_t cap;
+};
+// Waves of a workgroup of the segment's walk: lane 64 w + i of the workgroup is lane 64 w + i of tok_scan_lane, so a
+// literal round proves up to 64 kScanBatchWaves tokens and a match round 1024 kScanBatchWaves.  On one file, 4 waves
+// walked 2^20 consecutive match tokens in 0.719 ms against the one-wave kernel's 1.287 ms, and 131,072 literal tokens
+// of 8192 bytes in 0.677 ms against 1.846 ms (kbench KBENCH_UNTOKENS; DESIGN.md section 4 has 1, 8 and 16 waves).
+constexpr uint32_t kScanBatchWaves = 4;
+constexpr uint32_t kScanMaxWaves = 16;
+
+// A round of `waves` waves from what each wave found: full[w] its leading full lanes (0 .. 64), part[w] the ints of its
+// first other lane.  The run is the waves before the first one that is not full, and that wave's own count.
+RSH_HD int64_t tok_scan_combine(const uint32_t* full, const uint32_t* part, uint32_t waves, uint32_t per) {
+    int64_t m = 0;
+    for (uint32_t w = 0; w < waves; ++w) {
+        m += (int64_t)per * full[w];
+        if (full[w] < kScanLanes) return m + part[w];
+    }
+    return m;
 }
 
 // ---- unframing ----

@@ -6,7 +6,8 @@
 // the kernel fills one while the host copies the other into the caller's buffer, which need not be pinned.  The 20
 // trailer bytes (putInt(0), Sender.java:1316, and the file MD5, :1148) are written by the host.
 // rsh_tokens_frame_device writes the same window into device memory instead: the same spans, pointed straight at the
-// destination, in one launch without the staging.
+// destination, in one launch without the staging.  rsh_tokens_frame_batch_device does that for a segment: the spans of
+// all files in one launch, their trailers placed by one gather launch.
 #include "ctx.h"
 #include "options.h"
 #include "rsync_hip_debug.h"
@@ -279,6 +280,71 @@ int rsh_tokens_write_batch_device(rsh_ctx* ctx, rsh_token_job* jobs, int32_t njo
     RSH_CLAIM_KEEP(ctx);
     RSH_HIP(hipSetDevice(ctx->device));
     return tokens_write_batch_claimed(ctx, jobs, njobs);
+}
+
+// A segment's streams into device memory: every file's spans point straight at its d_out and run in one launch; the
+// trailers are staged behind the descriptors and placed as gather ops by one more launch.
+int rsh_tokens_frame_batch_device(rsh_ctx* ctx, rsh_token_frame_job* jobs, int32_t njobs) {
+    if (!ctx || njobs < 0 || (njobs > 0 && !jobs)) return RSH_E_INVAL;
+    RSH_CLAIM_KEEP(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    static_assert(sizeof(rsh_token_frame_job) == sizeof(rsh_token_job), "rsh_token_job with d_out for out");
+    constexpr size_t kSlot = 32;  // a staged trailer's bytes
+    std::vector<TokSpan> spans;
+    std::vector<int32_t> owner;
+    const int64_t span = span_bytes();
+    for (int32_t f = 0; f < njobs; ++f) {
+        rsh_token_frame_job& jb = jobs[f];
+        bool lit = false;
+        jb.out_len = 0;
+        jb.status = check_events(jb.ev, jb.n_ev, jb.n, &lit);
+        if (jb.status == RSH_OK && (lit && !jb.d_src)) jb.status = RSH_E_INVAL;
+        if (jb.status != RSH_OK) continue;
+        jb.out_len = rsh_tokens_size(jb.ev, jb.n_ev);
+        if (jb.out_cap < jb.out_len) jb.status = RSH_E_NOSPACE;
+        else if (!jb.d_out) jb.status = RSH_E_INVAL;
+        if (jb.status != RSH_OK) continue;
+        TokWork w;
+        w.d_src = static_cast<const uint8_t*>(jb.d_src);
+        w.ev = jb.ev;
+        w.n_ev = jb.n_ev;
+        if (jb.out_len > kTrailer) {
+            w.index_events();
+            plan_window(w, 0, jb.out_len - kTrailer, static_cast<uint8_t*>(jb.d_out), span, spans);
+        }
+        owner.push_back(f);
+    }
+    if (!owner.empty()) {
+        if (spans.size() > (size_t)INT32_MAX) return RSH_E_INVAL;
+        const size_t desc = (spans.size() * sizeof(TokSpan) + 15) & ~(size_t)15;
+        const size_t ops_at = desc + owner.size() * kSlot;
+        hipError_t e = ctx->h_tokd[0].ensure(ops_at + owner.size() * sizeof(GatherOp));
+        uint32_t max_len = 0;
+        if (e == hipSuccess) {
+            uint8_t* base = ctx->h_tokd[0].as<uint8_t>();
+            memcpy(base, spans.data(), spans.size() * sizeof(TokSpan));
+            for (const TokSpan& sp : spans) max_len = std::max(max_len, sp.len);
+            GatherOp* ops = reinterpret_cast<GatherOp*>(base + ops_at);
+            for (size_t k = 0; k < owner.size(); ++k) {
+                const rsh_token_frame_job& jb = jobs[owner[k]];
+                uint8_t* t = base + desc + k * kSlot;
+                write_trailer(jb.file_md5, jb.out_len, jb.out_len - kTrailer, kTrailer, t);
+                ops[k] = GatherOp{t, static_cast<uint8_t*>(jb.d_out) + (jb.out_len - kTrailer), kTrailer};
+            }
+            e = launch_token_frame(reinterpret_cast<const TokSpan*>(base), (uint32_t)spans.size(), max_len, false, ctx->stream);
+            if (e == hipSuccess) e = launch_gather_ops(ops, (uint32_t)owner.size(), ctx->stream, kTrailer);
+        }
+        const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the descriptors are read until the launches are done
+        if (e == hipSuccess) e = e2;
+        if (e != hipSuccess) {
+            note_error(e, __LINE__, "tokens.cpp");
+            for (int32_t f : owner) jobs[f].status = RSH_E_DEVICE;
+            return RSH_E_DEVICE;
+        }
+    }
+    for (int32_t f = 0; f < njobs; ++f)
+        if (jobs[f].status != RSH_OK) return jobs[f].status;
+    return RSH_OK;
 }
 
 }  // extern "C"

@@ -154,6 +154,21 @@ class TokenJob(ctypes.Structure):
                 ("out_len", ctypes.c_int64), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class TokenFrameJob(ctypes.Structure):
+    """rsh_token_frame_job: one file of rsh_tokens_frame_batch_device (device source and output, host events)."""
+    _fields_ = [("d_src", ctypes.c_void_p), ("n", ctypes.c_int64), ("ev", ctypes.c_void_p), ("n_ev", ctypes.c_int64),
+                ("file_md5", ctypes.c_uint8 * 16), ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_int64),
+                ("out_len", ctypes.c_int64), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class ResidentJob(ctypes.Structure):
+    """rsh_resident_job: one file of rsh_receiver_combine_batch_resident (every pointer a device pointer)."""
+    _fields_ = [("d_tokens", ctypes.c_void_p), ("tokens_len", ctypes.c_int64), ("h", Header),
+                ("d_replica", ctypes.c_void_p), ("replica_len", ctypes.c_int64), ("defer_write", ctypes.c_int32),
+                ("status", ctypes.c_int32), ("d_target", ctypes.c_void_p), ("target_cap", ctypes.c_int64),
+                ("res", CombineResult)]
+
+
 class Md5Job(ctypes.Structure):
     """rsh_md5_job: one file of rsh_file_md5_batch."""
     _fields_ = [("pieces", ctypes.POINTER(Piece)), ("npieces", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -164,6 +179,13 @@ class TokenRun(ctypes.Structure):
     """rsh_token_run: one record of the token walk's run list (rsh_debug_tokens_scan_selftest)."""
     _fields_ = [("pos", ctypes.c_int64), ("kind", ctypes.c_int32), ("value", ctypes.c_int32),
                 ("count", ctypes.c_int64)]
+
+
+class TokenScanJob(ctypes.Structure):
+    """rsh_token_scan_job: one file of the segment's token walk (rsh_debug_tokens_scan_batch_selftest)."""
+    _fields_ = [("tokens", ctypes.c_void_p), ("tokens_len", ctypes.c_int64), ("start", ctypes.c_int64),
+                ("runs", ctypes.c_void_p), ("cap", ctypes.c_int64), ("n_runs", ctypes.c_int64), ("pos", ctypes.c_int64),
+                ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 COMBINE_NO_MD5 = 1
@@ -182,12 +204,14 @@ EXPORTS = ["rsh_abi_version", "rsh_strerror", "rsh_last_error", "rsh_device_coun
            "rsh_tokens_write_device", "rsh_tokens_write_kept", "rsh_tokens_write_batch_device",
            "rsh_sums_wire_size", "rsh_header_from_wire", "rsh_sums_frame_device", "rsh_sums_unframe_device",
            "rsh_block_sums_batch_wire", "rsh_match_scan_batch_wire", "rsh_block_sums_batch_wire_multi",
-           "rsh_match_scan_batch_wire_multi", "rsh_tokens_frame_device", "rsh_receiver_combine_resident"]
+           "rsh_match_scan_batch_wire_multi", "rsh_tokens_frame_device", "rsh_receiver_combine_resident",
+           "rsh_tokens_frame_batch_device", "rsh_receiver_combine_batch_resident"]
 # include/rsync_hip_debug.h (testing / diagnostics ABI)
 DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_reset_options", "rsh_debug_k1_clock",
                  "rsh_debug_streams_busy", "rsh_debug_kernel_ms", "rsh_debug_multi_selftest", "rsh_debug_generation",
                  "rsh_debug_tokens_selftest", "rsh_debug_sums_selftest", "rsh_debug_tokens_scan_selftest",
-                 "rsh_debug_untokens_selftest", "rsh_debug_k1_dma_swizzle", "rsh_debug_k1_wave_times"]
+                 "rsh_debug_untokens_selftest", "rsh_debug_k1_dma_swizzle", "rsh_debug_k1_wave_times",
+                 "rsh_debug_tokens_scan_batch_selftest"]
 
 _LIB = None
 
@@ -313,6 +337,9 @@ def lib():
                                             ctypes.POINTER(I64), ctypes.POINTER(I32)], ctypes.c_int),
         "rsh_debug_untokens_selftest": ([P, P, I64, I64, I32, I64, P, I64, ctypes.POINTER(I64), ctypes.POINTER(I64),
                                          ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_tokens_frame_batch_device": ([P, ctypes.POINTER(TokenFrameJob), I32], ctypes.c_int),
+        "rsh_receiver_combine_batch_resident": ([P, ctypes.POINTER(ResidentJob), I32, I32], ctypes.c_int),
+        "rsh_debug_tokens_scan_batch_selftest": ([P, ctypes.POINTER(TokenScanJob), I32, P, I32, I32], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -478,6 +505,34 @@ def tokens_scan_selftest(tokens, length, start=0, cap=1 << 16, ctx=None):
     _check(lib().rsh_debug_tokens_scan_selftest(None if ctx is None else ctx.handle, _addr(tokens), length, start, runs,
                                                 cap, ctypes.byref(n), ctypes.byref(pos), ctypes.byref(st)))
     return [(r.pos, r.kind, r.value, r.count) for r in runs[:n.value]], pos.value, st.value
+
+
+def tokens_scan_batch_selftest(jobs, live=None, lanes=0, ctx=None):
+    """rsh_debug_tokens_scan_batch_selftest: one pass of the segment's token walk over the files `live` (indices into
+    jobs; None: all).  jobs = [(tokens, length, start, cap[, runs])].  ctx None: tokens are uint8 arrays walked by the
+    host stand-in with a round of `lanes` lanes (0: the kernel's width), and the result is [(records or None, end
+    position, status)] per job, None and -1, -1 for a file that did not walk.  With a Context: tokens and runs are
+    DeviceBuffers or device addresses (runs: room for cap records of 24 bytes), token_scan_batch_kernel walks all the
+    files in one launch, and the result is [(record count, end position, status)]; the records stay on the device."""
+    n = len(jobs)
+    tj = (TokenScanJob * max(n, 1))()
+    keep = []
+    for i, job in enumerate(jobs):
+        tokens, length, start, cap = job[:4]
+        if ctx is None:
+            runs = (TokenRun * cap)()
+            keep.append(runs)
+            tj[i].runs = ctypes.addressof(runs)
+        else:
+            tj[i].runs = _addr(job[4]).value
+        tj[i].tokens, tj[i].tokens_len, tj[i].start, tj[i].cap = _addr(tokens).value, length, start, cap
+    order = np.ascontiguousarray(range(n) if live is None else live, dtype=np.int32)
+    _check(lib().rsh_debug_tokens_scan_batch_selftest(None if ctx is None else ctx.handle, tj, n,
+                                                      _ptr(order) if order.size else None, order.size, lanes))
+    if ctx is not None:
+        return [(tj[i].n_runs, tj[i].pos, tj[i].status) for i in range(n)]
+    return [([(r.pos, r.kind, r.value, r.count) for r in keep[i][:tj[i].n_runs]] if tj[i].n_runs >= 0 else None,
+             tj[i].pos, tj[i].status) for i in range(n)]
 
 
 def untokens_selftest(tokens, length, pos, T, count, out, span=0, ctx=None):
@@ -853,6 +908,38 @@ class Context:
                                                  _addr(d_replica), replica_len, int(bool(defer_write)),
                                                  _addr(d_target), target_cap, flags, ctypes.byref(r))
         return rc, r
+
+    def receiver_combine_batch_resident(self, jobs, flags=0):
+        """rsh_receiver_combine_batch_resident: a segment's Receiver with every stream, replica and target in HBM.
+        jobs = [(d_tokens, tokens_len, Header, d_replica or None, replica_len, d_target, target_cap[, defer_write])]
+        (DeviceBuffers or device addresses) -> (the call's status, [(status, CombineResult)]).  Nothing is raised."""
+        rj = (ResidentJob * max(len(jobs), 1))()
+        for i, job in enumerate(jobs):
+            d_tok, tok_len, h, d_rep, rep_len, d_tgt, cap = job[:7]
+            j = rj[i]
+            j.d_tokens, j.tokens_len, j.h = _addr(d_tok).value, tok_len, h
+            j.d_replica, j.replica_len = _addr(d_rep).value, rep_len
+            j.d_target, j.target_cap = _addr(d_tgt).value, cap
+            j.defer_write = int(bool(job[7])) if len(job) > 7 else 0
+        rc = lib().rsh_receiver_combine_batch_resident(self._p, rj, len(jobs), flags)
+        return rc, [(rj[i].status, CombineResult.from_buffer_copy(rj[i].res)) for i in range(len(jobs))]
+
+    def tokens_frame_batch_device(self, jobs):
+        """rsh_tokens_frame_batch_device: a segment's streams framed into device memory in one call.
+        jobs = [(d_src, n, ev, md5, d_out[, out_cap])] (DeviceBuffers or device addresses; out_cap: the capacity to
+        offer instead of the stream's size) -> (the call's status, [(status, out_len)])."""
+        tj = (TokenFrameJob * max(len(jobs), 1))()
+        keep = []
+        for i, job in enumerate(jobs):
+            d, n, ev, md5, d_out = job[:5]
+            ev = np.ascontiguousarray(ev, dtype=EVENT_DTYPE)
+            keep.append(ev)
+            tj[i].d_src, tj[i].n = _addr(d).value, n
+            tj[i].ev, tj[i].n_ev = (ev.ctypes.data if ev.size else None), ev.size
+            tj[i].file_md5[:] = list(bytes(md5))
+            tj[i].d_out, tj[i].out_cap = _addr(d_out).value, job[5] if len(job) > 5 else tokens_size(ev)
+        rc = lib().rsh_tokens_frame_batch_device(self._p, tj, len(jobs))
+        return rc, [(tj[i].status, tj[i].out_len) for i in range(len(jobs))]
 
     def tokens_kept(self, ev, md5, start=0, length=None):
         """rsh_tokens_write_kept: as tokens_device over the source this context's last single-file scan left in HBM;

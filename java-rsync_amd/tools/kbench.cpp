@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <vector>
 
 #include "device.h"
@@ -173,6 +174,129 @@ static int tokens_main(int argc, char** argv) {
 //     production gather copying the same number of bytes in 1 MiB ops, alternating rep by rep;
 //   * token_scan_kernel walking it, and walking a stream of 2^20 consecutive match tokens, each against a
 //     device-to-host copy of the same stream (the download a host walk needs), into pageable and into pinned memory.
+//   * token_scan_batch_kernel on one file at 1, 4, 8 and 16 waves to a round against token_scan_kernel, rep by rep;
+//   * KBENCH_UNTOKENS_FILES=<n>: the walk of a segment of n streams of config 4's shape (128 MiB files at
+//     B = 8192: half of them identical -- 16384 consecutive match tokens -- and half with every other block replaced
+//     -- a match token and an 8192-byte literal token in turn, 16384 records), as the library drives it:
+//     rsh_receiver_combine_batch_resident's rounds (one launch for all files at 4096 records each, one download of the
+//     TokScanOuts, one copy launch of the records) against rsh_receiver_combine_resident's per file (a launch at 65536
+//     records and two small downloads each), wall time.
+static bool segment_walk(int nfiles, int reps, hipStream_t s) {
+    const int64_t blocks = 16384, T = 8192;
+    std::vector<uint8_t> ident((size_t)(4 * blocks + 4), 0), half;
+    auto put = [](std::vector<uint8_t>& v, size_t at, int32_t x) { memcpy(v.data() + at, &x, 4); };
+    for (int64_t b = 0; b < blocks; ++b) put(ident, (size_t)(4 * b), (int32_t)(-(b + 1)));
+    half.assign((size_t)(blocks / 2 * (4 + 4 + T) + 4), 0x5A);
+    for (int64_t b = 0; b < blocks; b += 2) {
+        const size_t at = (size_t)(b / 2 * (8 + T));
+        put(half, at, (int32_t)(-(b + 1)));
+        put(half, at + 4, (int32_t)T);
+    }
+    put(half, half.size() - 4, 0);
+    std::vector<uint8_t*> d_st((size_t)nfiles);
+    std::vector<int64_t> lens((size_t)nfiles);
+    for (int f = 0; f < nfiles; ++f) {  // every file its own copy: no stream's lines are another's cache hits
+        const std::vector<uint8_t>& v = f % 2 ? half : ident;
+        lens[(size_t)f] = (int64_t)v.size();
+        CK(hipMalloc(&d_st[(size_t)f], v.size()));
+        if (f < 2) CK(hipMemcpy(d_st[(size_t)f], v.data(), v.size(), hipMemcpyHostToDevice));
+        else CK(hipMemcpy(d_st[(size_t)f], d_st[(size_t)(f % 2)], v.size(), hipMemcpyDeviceToDevice));
+    }
+    const int64_t capb = 4096, cap1 = 64 << 10;
+    const size_t stride = (size_t)capb * sizeof(rsh::TokRun);
+    uint8_t *d_runs, *h_runs, *d_runs1, *h_runs1;
+    rsh::TokScanOut *d_outs, *h_outs, *d_out1, *h_out1;
+    rsh::TokScanJob* jobs;
+    int32_t* live;
+    rsh::CopyEnt* ents;
+    CK(hipMalloc(&d_runs, (size_t)nfiles * stride));
+    CK(hipHostMalloc(&h_runs, (size_t)nfiles * stride, hipHostMallocDefault));
+    CK(hipMalloc(&d_runs1, (size_t)cap1 * sizeof(rsh::TokRun)));
+    CK(hipHostMalloc(&h_runs1, (size_t)cap1 * sizeof(rsh::TokRun), hipHostMallocDefault));
+    CK(hipMalloc(&d_outs, (size_t)nfiles * sizeof(rsh::TokScanOut)));
+    CK(hipHostMalloc(&h_outs, (size_t)nfiles * sizeof(rsh::TokScanOut), hipHostMallocDefault));
+    CK(hipMalloc(&d_out1, sizeof(rsh::TokScanOut)));
+    CK(hipHostMalloc(&h_out1, sizeof(rsh::TokScanOut), hipHostMallocDefault));
+    CK(hipHostMalloc(&jobs, (size_t)nfiles * sizeof(rsh::TokScanJob), hipHostMallocDefault));
+    CK(hipHostMalloc(&live, (size_t)nfiles * sizeof(int32_t), hipHostMallocDefault));
+    CK(hipHostMalloc(&ents, (size_t)nfiles * sizeof(rsh::CopyEnt), hipHostMallocDefault));
+    double tot[2] = {0, 0}, best[2] = {1e30, 1e30};
+    int64_t records[2] = {0, 0}, rounds = 0;
+    bool ok = true;
+    for (int r = 0; r < reps + 1; ++r) {  // (the first round warms both up)
+        for (int k = 0; k < 2; ++k) {
+            CK(hipStreamSynchronize(s));
+            const auto t0 = std::chrono::steady_clock::now();
+            int64_t recs = 0;
+            if (k == 0) {
+                std::vector<int32_t> cur;
+                for (int f = 0; f < nfiles; ++f) {
+                    jobs[f] = rsh::TokScanJob{d_st[(size_t)f], lens[(size_t)f], 0,
+                                              reinterpret_cast<rsh::TokRun*>(d_runs + (size_t)f * stride), capb};
+                    cur.push_back(f);
+                }
+                rounds = 0;
+                while (!cur.empty()) {
+                    memcpy(live, cur.data(), cur.size() * sizeof(int32_t));
+                    CK(rsh::launch_token_scan_batch(jobs, live, (uint32_t)cur.size(), d_outs, s));
+                    CK(hipMemcpyAsync(h_outs, d_outs, (size_t)nfiles * sizeof(rsh::TokScanOut), hipMemcpyDeviceToHost, s));
+                    CK(hipStreamSynchronize(s));
+                    uint32_t ne = 0;
+                    int64_t mx = 0;
+                    for (int32_t f : cur) {
+                        const int64_t bytes = h_outs[f].n * (int64_t)sizeof(rsh::TokRun);
+                        if (bytes <= 0) continue;
+                        ents[ne++] = rsh::CopyEnt{d_runs + (size_t)f * stride, h_runs + (size_t)f * stride, bytes};
+                        mx = std::max(mx, bytes);
+                    }
+                    CK(rsh::launch_copy_many(ents, ne, mx, s));
+                    CK(hipStreamSynchronize(s));
+                    std::vector<int32_t> next;
+                    for (int32_t f : cur) {
+                        recs += h_outs[f].n;
+                        if (h_outs[f].status == rsh::TOK_SCAN_MORE) {
+                            jobs[f].from = h_outs[f].pos;
+                            next.push_back(f);
+                        } else {
+                            ok = ok && h_outs[f].status == rsh::TOK_SCAN_END && h_outs[f].pos == lens[(size_t)f];
+                        }
+                    }
+                    cur.swap(next);
+                    ++rounds;
+                }
+            } else {
+                for (int f = 0; f < nfiles; ++f) {
+                    int64_t from = 0;
+                    do {
+                        CK(rsh::launch_token_scan(d_st[(size_t)f], lens[(size_t)f], from, reinterpret_cast<rsh::TokRun*>(d_runs1),
+                                                  cap1, d_out1, s));
+                        CK(hipMemcpyAsync(h_out1, d_out1, sizeof(rsh::TokScanOut), hipMemcpyDeviceToHost, s));
+                        CK(hipStreamSynchronize(s));
+                        if (h_out1->n > 0) {
+                            CK(hipMemcpyAsync(h_runs1, d_runs1, (size_t)h_out1->n * sizeof(rsh::TokRun), hipMemcpyDeviceToHost, s));
+                            CK(hipStreamSynchronize(s));
+                        }
+                        recs += h_out1->n;
+                        from = h_out1->pos;
+                    } while (h_out1->status == rsh::TOK_SCAN_MORE);
+                    ok = ok && h_out1->status == rsh::TOK_SCAN_END && from == lens[(size_t)f];
+                }
+            }
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            records[k] = recs;
+            if (r == 0) continue;
+            tot[k] += ms;
+            best[k] = std::min(best[k], ms);
+        }
+    }
+    ok = ok && records[0] == records[1];
+    printf("segment walk files=%d records=%lld  batch (%lld rounds) avg %.3f ms best %.3f ms  single-file calls avg %.3f ms "
+           "best %.3f ms  batch / single %.3f  %s\n",
+           nfiles, (long long)records[0], (long long)rounds, tot[0] / reps, best[0], tot[1] / reps, best[1], tot[0] / tot[1],
+           ok ? "walk=ok" : "walk=MISMATCH");
+    return ok;
+}
+
 static int untokens_main(int argc, char** argv) {
     const int64_t count = ((int64_t)atoll(argv[1]) << 20) / rsh::kTokStride;  // whole tokens
     const int64_t n = count * rsh::kTokData, slen = count * rsh::kTokStride + 4;
@@ -299,6 +423,50 @@ static int untokens_main(int argc, char** argv) {
                w ? "matches" : "literals", (long long)len, t[0] / reps, bt[0], t[0] / reps * (double)(1 << 30) / (double)len,
                t[1] / reps, t[2] / reps, t[0] / t[2], (long long)so.n, ok ? "walk=ok" : "walk=MISMATCH");
     }
+    // the segment's walk on one file (token_scan_batch_kernel at 1, 4, 8 and 16 waves to a round) against the one-wave
+    // token_scan_kernel over the same two streams, alternating rep by rep
+    rsh::TokScanJob* pj;
+    int32_t* plive;
+    rsh::TokScanOut* d_bout;
+    CK(hipHostMalloc(&pj, sizeof(rsh::TokScanJob), hipHostMallocDefault));
+    CK(hipHostMalloc(&plive, sizeof(int32_t), hipHostMallocDefault));
+    CK(hipMalloc(&d_bout, sizeof(rsh::TokScanOut)));
+    plive[0] = 0;
+    for (int w = 0; w < 2; ++w) {
+        const uint8_t* st = w ? mstream : stream;
+        const int64_t len = w ? mlen : slen;
+        *pj = rsh::TokScanJob{st, len, 0, d_runs, 1024};
+        for (uint32_t waves : {1u, 4u, 8u, 16u}) {
+            float t[2] = {0, 0}, bt[2] = {1e30f, 1e30f};
+            for (int r = 0; r < reps + 1; ++r) {
+                for (int k = 0; k < 2; ++k) {
+                    CK(hipStreamSynchronize(s));
+                    CK(hipEventRecord(e0, s));
+                    if (k == 0) CK(rsh::launch_token_scan(st, len, 0, d_runs, 1024, d_out, s));
+                    else CK(rsh::launch_token_scan_batch_variant(waves, pj, plive, 1, d_bout, s));
+                    CK(hipEventRecord(e1, s));
+                    CK(hipEventSynchronize(e1));
+                    float ms;
+                    CK(hipEventElapsedTime(&ms, e0, e1));
+                    if (r == 0) continue;
+                    t[k] += ms;
+                    bt[k] = ms < bt[k] ? ms : bt[k];
+                }
+            }
+            rsh::TokScanOut so;
+            rsh::TokRun run;
+            CK(hipMemcpy(&so, d_bout, sizeof(so), hipMemcpyDeviceToHost));
+            CK(hipMemcpy(&run, d_runs, sizeof(run), hipMemcpyDeviceToHost));
+            const bool ok = so.status == rsh::TOK_SCAN_END && so.pos == len && so.n == 1 &&
+                            run.count == (w ? nmatch : count) && run.v == (w ? 5 : (int32_t)rsh::kTokData);
+            walk_ok = walk_ok && ok;
+            printf("token_scan_batch %-8s waves=%-2u  one wave avg %.3f ms best %.3f ms  batch avg %.3f ms best %.3f ms  "
+                   "batch / one wave %.3f  %s\n",
+                   w ? "matches" : "literals", waves, t[0] / reps, bt[0], t[1] / reps, bt[1], t[1] / t[0],
+                   ok ? "walk=ok" : "walk=MISMATCH");
+        }
+    }
+    if (getenv("KBENCH_UNTOKENS_FILES")) walk_ok = segment_walk(atoi(getenv("KBENCH_UNTOKENS_FILES")), reps, s) && walk_ok;
     return same && walk_ok ? 0 : 1;
 }
 
