@@ -7,7 +7,8 @@
  * Tests force rare paths with them; a few are tunables: k1_gather, k1_shift,
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
- * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio, tokens_runs_batch, resident_md5_bytes.
+ * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio, tokens_runs_batch, resident_md5_bytes,
+ * scan_phase_map.
  *
  * k1_dma = 1 (default): the main waves of the pipelined K1 stream their stages from HBM straight into LDS wherever
  * every wave's base is 16-B aligned; 0: the register-staged form at every base (the A/B partner, from one library).
@@ -41,7 +42,8 @@ void rsh_debug_reset_options(void);
 
 /* The duration of a K1 from its own dispatch timestamps (HIP events recorded by the launch, hipExtLaunchKernelGGL):
  * which 0 = the last rsh_block_sums_device's K1 (the Generator), 1 = the last single-file scan's aligned speculation
- * when it ran to completion, 2 = the last sums_frame_kernel / sums_unframe_kernel launch (HIP events around it).
+ * when it ran to completion, 2 = the last sums_frame_kernel / sums_unframe_kernel launch (HIP events around it),
+ * 3 = the phase_map_kernel launch of the last rsh_debug_phase_map_selftest with a context (HIP events around it).
  * *ms = -1 when that launch was not timed (a shape whose kernel takes no events). */
 int rsh_debug_kernel_ms(rsh_ctx* ctx, int32_t which, double* ms);
 
@@ -149,6 +151,40 @@ int rsh_debug_tokens_scan_batch_selftest(rsh_ctx* ctx, rsh_token_scan_job* jobs,
  * and the kernel (lo, hi untouched).  *n_desc: the descriptor count. */
 int rsh_debug_untokens_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t pos, int32_t T,
                                 int64_t count, uint8_t* out, int64_t span, int64_t* n_desc, int64_t* lo, int64_t* hi);
+
+/* The phase map of a single-file scan (option scan_phase_map = k > 0: once k phase-shifted speculations have gone out,
+ * the next hint that nothing covers maps the rest of the source; 0, the default: never).  A sample at position a keys
+ * the positions [a, a + 2 B) whose window is full and looks them up in the table; its anchor is the smallest p in
+ * [a, a + B) such that windows p and p + B carry chunks i and i + 1 (chunks whose weak sum another chunk has are
+ * ignored).  status: 0 none, 1 found (p, i), 2 overflow (more than 128 hits: low-entropy data). */
+typedef struct {
+    int64_t p;      /* found: the anchor's position; else -1 */
+    int32_t i;      /* found: its chunk; else -1 */
+    int32_t status;
+} rsh_phase_anchor;
+/* A stretch of a plan: windows s0 + k B, k < count, against chunks pref0 + k; waves: its K1Seg waves of 64 windows in
+ * the plan's launch (the other windows are K1Tail entries; 0 from the planner alone). */
+typedef struct {
+    int64_t s0, count, pref0, waves;
+} rsh_phase_seg;
+/* The plan of the context's last single-file scan (*n_segs = 0 when its map did not engage or found nothing). */
+int rsh_debug_phase_plan(rsh_ctx* ctx, rsh_phase_seg* segs, int64_t cap, int64_t* n_segs);
+/* The kernel's host stand-in (phase_map.h) over the host source src[0, n) and the table's weak sums, one record per
+ * sample position into host_out.  With a context, phase_map_kernel too: the source is copied to HBM at base_offset
+ * (0 .. 255) bytes past a 256-byte boundary, the chunk index is built as the scan builds it, and the kernel's records
+ * over the same samples go to dev_out.  rsh_debug_kernel_ms(ctx, 3, ..) then gives that launch's duration. */
+int rsh_debug_phase_map_selftest(rsh_ctx* ctx, const uint8_t* src, int64_t n, int32_t block_length, const int32_t* weak,
+                                 int32_t chunk_count, const int64_t* samples, int64_t n_samples, int32_t base_offset,
+                                 rsh_phase_anchor* host_out, rsh_phase_anchor* dev_out);
+/* The planner without a device.  Round B: from round A's samples (ascending positions) and their records, the
+ * positions of the second round's samples, at most `cap` of them in all (a gap that does not fit, and every later one,
+ * stays uncovered).  Segments: the plan from both rounds' samples merged in ascending order; lo: no stretch starts
+ * below it; min_windows: shorter stretches are dropped (the scan uses 8). */
+int rsh_debug_phase_round_b(const int64_t* samples, const rsh_phase_anchor* anchors, int64_t count, int64_t n,
+                            int32_t block_length, int64_t cap, int64_t* out, int64_t out_cap, int64_t* n_out);
+int rsh_debug_phase_segments(const int64_t* samples, const rsh_phase_anchor* anchors, int64_t count, int64_t lo,
+                             int64_t n, int32_t block_length, int32_t chunk_count, int64_t min_windows,
+                             rsh_phase_seg* segs, int64_t cap, int64_t* n_segs);
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,8 @@ int rsh_ctx_create(int device, rsh_ctx** out) {
         hipEventCreateWithFlags(&c->ev_rs_tail, hipEventDisableTiming) != hipSuccess ||
         hipEventCreate(&c->ev_pha[0]) != hipSuccess || hipEventCreate(&c->ev_phb[0]) != hipSuccess ||
         hipEventCreate(&c->ev_pha[1]) != hipSuccess || hipEventCreate(&c->ev_phb[1]) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_pm, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreate(&c->ev_pma) != hipSuccess || hipEventCreate(&c->ev_pmb) != hipSuccess ||
         hipExtMallocWithFlags(reinterpret_cast<void**>(&c->abort_word), 256, hipDeviceMallocUncached) != hipSuccess ||
         hipMemset(c->abort_word, 0, 256) != hipSuccess ||  // generations start at 1
         // recorded once, so that a launch may always wait for its buffer set's previous launch
@@ -547,12 +549,12 @@ int32_t rsh_debug_k1_dma_swizzle(int32_t what, int32_t chunk, int32_t index) {
 }
 
 int rsh_debug_kernel_ms(rsh_ctx* ctx, int32_t which, double* ms) {
-    if (!ctx || !ms || which < 0 || which > 2) return RSH_E_INVAL;
+    if (!ctx || !ms || which < 0 || which > 3) return RSH_E_INVAL;
     *ms = -1.0;
-    const bool timed = which == 0 ? ctx->gen_timed : which == 1 ? ctx->spec_timed : ctx->sums_timed;
+    const bool timed = which == 0 ? ctx->gen_timed : which == 1 ? ctx->spec_timed : which == 2 ? ctx->sums_timed : ctx->pm_timed;
     if (!timed) return RSH_OK;
-    const hipEvent_t a = which == 0 ? ctx->ev_gen_a : which == 1 ? ctx->ev_k1a : ctx->ev_sums_a;
-    const hipEvent_t b = which == 0 ? ctx->ev_gen_b : which == 1 ? ctx->ev_k1b : ctx->ev_sums_b;
+    const hipEvent_t a = which == 0 ? ctx->ev_gen_a : which == 1 ? ctx->ev_k1a : which == 2 ? ctx->ev_sums_a : ctx->ev_pma;
+    const hipEvent_t b = which == 0 ? ctx->ev_gen_b : which == 1 ? ctx->ev_k1b : which == 2 ? ctx->ev_sums_b : ctx->ev_pmb;
     RSH_HIP(hipSetDevice(ctx->device));
     RSH_HIP(hipEventSynchronize(b));
     float f = 0.f;
@@ -632,6 +634,111 @@ int rsh_debug_k1_wave_times(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     for (void* p : {w, st, rec})
         if (p) (void)hipFree(p);
+    RSH_HIP(e);
+    return RSH_OK;
+}
+
+static_assert(sizeof(rsh_phase_anchor) == sizeof(rsh::PhaseAnchor), "rsh_phase_anchor is the device record");
+
+int rsh_debug_phase_plan(rsh_ctx* ctx, rsh_phase_seg* segs, int64_t cap, int64_t* n_segs) {
+    if (!ctx || !n_segs || cap < 0 || (cap > 0 && !segs)) return RSH_E_INVAL;
+    RSH_CLAIM_KEEP(ctx);
+    *n_segs = (int64_t)ctx->last_plan.size();
+    if (*n_segs > cap) return RSH_E_NOSPACE;
+    for (size_t i = 0; i < ctx->last_plan.size(); ++i) {
+        const rsh_ctx::PlanSeg& q = ctx->last_plan[i];
+        segs[i] = rsh_phase_seg{q.g.s0, q.g.count, q.g.pref0, q.waves};
+    }
+    return RSH_OK;
+}
+
+static bool phase_lists_ok(const int64_t* samples, const void* anchors, int64_t count, int64_t n, int32_t B) {
+    if (count < 0 || (count > 0 && (!samples || !anchors)) || n < 0 || B <= 0) return false;
+    for (int64_t j = 0; j < count; ++j)
+        if (samples[j] < 0 || (j > 0 && samples[j] <= samples[j - 1])) return false;
+    return true;
+}
+
+int rsh_debug_phase_round_b(const int64_t* samples, const rsh_phase_anchor* anchors, int64_t count, int64_t n,
+                            int32_t block_length, int64_t cap, int64_t* out, int64_t out_cap, int64_t* n_out) {
+    if (!phase_lists_ok(samples, anchors, count, n, block_length) || !n_out || cap < 0 || out_cap < 0) return RSH_E_INVAL;
+    std::vector<rsh::PhaseSample> sa((size_t)count), sb;
+    for (int64_t j = 0; j < count; ++j) sa[(size_t)j].a = samples[j];
+    rsh::phase_round_b(sa.data(), reinterpret_cast<const rsh::PhaseAnchor*>(anchors), count, n, block_length, cap, &sb);
+    *n_out = (int64_t)sb.size();
+    if (*n_out > out_cap || (*n_out > 0 && !out)) return RSH_E_NOSPACE;
+    for (size_t j = 0; j < sb.size(); ++j) out[j] = sb[j].a;
+    return RSH_OK;
+}
+
+int rsh_debug_phase_segments(const int64_t* samples, const rsh_phase_anchor* anchors, int64_t count, int64_t lo,
+                             int64_t n, int32_t block_length, int32_t chunk_count, int64_t min_windows,
+                             rsh_phase_seg* segs, int64_t cap, int64_t* n_segs) {
+    if (!phase_lists_ok(samples, anchors, count, n, block_length) || !n_segs || cap < 0 || lo < 0 || chunk_count < 0)
+        return RSH_E_INVAL;
+    std::vector<rsh::PhaseSample> sa((size_t)count);
+    for (int64_t j = 0; j < count; ++j) sa[(size_t)j].a = samples[j];
+    std::vector<rsh::PhaseSeg> g;
+    rsh::phase_plan(sa.data(), reinterpret_cast<const rsh::PhaseAnchor*>(anchors), count, lo, n, block_length, chunk_count,
+                    min_windows, &g);
+    *n_segs = (int64_t)g.size();
+    if (*n_segs > cap || (*n_segs > 0 && !segs)) return RSH_E_NOSPACE;
+    for (size_t j = 0; j < g.size(); ++j) segs[j] = rsh_phase_seg{g[j].s0, g[j].count, g[j].pref0, 0};
+    return RSH_OK;
+}
+
+int rsh_debug_phase_map_selftest(rsh_ctx* ctx, const uint8_t* src, int64_t n, int32_t block_length, const int32_t* weak,
+                                 int32_t chunk_count, const int64_t* samples, int64_t n_samples, int32_t base_offset,
+                                 rsh_phase_anchor* host_out, rsh_phase_anchor* dev_out) {
+    if (!src || n <= 0 || block_length <= 0 || block_length > kMaxBlockLength || !weak || chunk_count <= 0 ||
+        n_samples < 0 || n_samples > (1 << 24) || (n_samples > 0 && (!samples || !host_out)) || base_offset < 0 ||
+        base_offset > 255 || (ctx && n_samples > 0 && !dev_out))
+        return RSH_E_INVAL;
+    for (int64_t j = 0; j < n_samples; ++j)
+        if (samples[j] < 0) return RSH_E_INVAL;
+    std::vector<rsh::PhaseSample> sa((size_t)n_samples);
+    for (int64_t j = 0; j < n_samples; ++j) sa[(size_t)j].a = samples[j];
+    rsh::phase_map_host(src, n, block_length, weak, chunk_count, sa.data(), n_samples,
+                        reinterpret_cast<rsh::PhaseAnchor*>(host_out));
+    if (!ctx || n_samples == 0) return RSH_OK;
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    // the source at base_offset past a 256-byte boundary of an allocation of its own; the table's sums, the chunk
+    // index and the records in another; the samples and the index descriptor in pinned memory, as the scan has them
+    const uint32_t ns = pow2_at_least(4 * (uint64_t)chunk_count + 2);
+    const size_t at_index = ((size_t)chunk_count * 4 + 255) & ~(size_t)255;
+    const size_t at_rec = at_index + (((size_t)ns * 8 + (size_t)chunk_count + 255) & ~(size_t)255);
+    void *d_src = nullptr, *d_tab = nullptr, *h_pin = nullptr;
+    hipError_t e = hipMalloc(&d_src, (size_t)n + 512);
+    if (e == hipSuccess) e = hipMalloc(&d_tab, at_rec + (size_t)n_samples * sizeof(rsh::PhaseAnchor));
+    if (e == hipSuccess) e = hipHostMalloc(&h_pin, 64 + (size_t)n_samples * sizeof(rsh::PhaseSample), hipHostMallocDefault);
+    if (e == hipSuccess) {
+        uint8_t* x = static_cast<uint8_t*>(d_src) + 256 + base_offset;
+        uint8_t* tab = static_cast<uint8_t*>(d_tab);
+        auto* slots = reinterpret_cast<unsigned long long*>(tab + at_index);
+        uint8_t* dup = reinterpret_cast<uint8_t*>(slots + ns);
+        auto* rec = reinterpret_cast<rsh::PhaseAnchor*>(tab + at_rec);
+        auto* ent = static_cast<rsh::ChunkIndexEnt*>(h_pin);
+        auto* hs = reinterpret_cast<rsh::PhaseSample*>(static_cast<uint8_t*>(h_pin) + 64);
+        *ent = rsh::ChunkIndexEnt{rsh::TableEnt{slots, reinterpret_cast<const int32_t*>(tab), ns - 1, chunk_count}, dup};
+        memcpy(hs, sa.data(), (size_t)n_samples * sizeof(rsh::PhaseSample));
+        hipStream_t s = ctx->stream;
+        e = hipMemcpyAsync(x, src, (size_t)n, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(tab, weak, (size_t)chunk_count * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(slots, 0, (size_t)ns * 8 + (size_t)chunk_count, s);
+        if (e == hipSuccess) e = rsh::launch_chunk_index(ent, 1, chunk_count, s);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_pma, s);
+        if (e == hipSuccess)
+            e = rsh::launch_phase_map(x, n, (uint32_t)block_length, slots, ns - 1, dup, hs, (uint32_t)n_samples, rec, s);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev_pmb, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(dev_out, rec, (size_t)n_samples * sizeof(rsh::PhaseAnchor), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        ctx->pm_timed = e == hipSuccess;
+    }
+    if (d_src) (void)hipFree(d_src);
+    if (d_tab) (void)hipFree(d_tab);
+    if (h_pin) (void)hipHostFree(h_pin);
     RSH_HIP(e);
     return RSH_OK;
 }

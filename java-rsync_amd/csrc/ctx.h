@@ -16,6 +16,7 @@
 #include "device.h"
 #include "hit_cache.h"
 #include "options.h"
+#include "phase_map.h"
 #include "resolver.h"
 #include "rsync_hip.h"
 
@@ -219,6 +220,20 @@ struct rsh_ctx {
     hipEvent_t ev_rs_tail = nullptr;  // the end of a single-file scan's work on aux (see spec_buffers_free)
     hipEvent_t ev_pha[2] = {nullptr, nullptr}, ev_phb[2] = {nullptr, nullptr};  // timing: set i's phase K1 (stats)
     int ph_set = 0;  // the buffer set of the latest phase launch
+    // The phase map (phase_map.h; HipBackend::map_rest): the file's chunk index and the anchor records in HBM, the
+    // plan's own sums and K1 descriptors, their host sides (h_pm: the samples, the index descriptor and the anchors'
+    // copy), the plan launch's events (landed; its K1's start and end) and the plan itself (rsh_debug_phase_plan)
+    DevBuf pm_index, pm_anchor, pm_weak, pm_strong, pm_segs;
+    PinnedBuf h_pm, h_pmw, h_pms, h_pm_segs;
+    hipEvent_t ev_pm = nullptr, ev_pma = nullptr, ev_pmb = nullptr;
+    static constexpr int kPlanWord = 32;  // the plan launch polls abort_word[kPlanWord] (its own 64-B line)
+    struct PlanSeg {
+        rsh::PhaseSeg g;
+        int64_t off;    // its sums: windows [off, off + g.count) of the plan's arrays
+        int64_t waves;  // its K1Seg waves (the rest: K1Tail entries)
+    };
+    std::vector<PlanSeg> last_plan;
+    bool pm_timed = false;  // ev_pma / ev_pmb belong to the last rsh_debug_phase_map_selftest's kernel
     PinnedBuf h_weak, h_strong, h_aw, h_as, h_fl;
     PinnedBuf h_pw[2], h_ps[2];  // the phase-shifted speculation's sums (host copies), per set
     PinnedBuf h_segs;      // staging of the segmented K1 descriptors
@@ -292,12 +307,14 @@ struct rsh_ctx {
         for (DevBuf* b : {&data, &weak, &strong, &src_weak, &src_strong, &flags, &ph_weak[0], &ph_strong[0],
                           &ph_weak[1], &ph_strong[1], &slots, &dslots,
                           &out, &first, &haw, &partials, &bucket, &seg_data, &seg_tab,
-                          &rcv[0], &rcv[1], &rcv_ops[0], &rcv_ops[1], &prep_dev, &fc_dev, &sums_raw, &tok_runs, &tokb_runs, &tokb_outs})
+                          &rcv[0], &rcv[1], &rcv_ops[0], &rcv_ops[1], &prep_dev, &fc_dev, &sums_raw, &tok_runs, &tokb_runs, &tokb_outs,
+                          &pm_index, &pm_anchor, &pm_weak, &pm_strong, &pm_segs})
             b->release();
         for (PinnedBuf* b : {&h_weak, &h_strong, &h_aw, &h_as, &h_fl, &h_pw[0], &h_ps[0], &h_pw[1], &h_ps[1], &h_lead, &h_pos, &h_out, &h_iv,
                              &h_tiles, &h_keys, &h_first, &h_win, &h_ptiles, &h_psegs, &h_hit, &h_win0, &h_pend, &h_bucket, &h_files,
                              &h_stage, &h_rcv_ops[0], &h_rcv_ops[1], &h_prep, &h_stamps, &h_fgw, &h_fjobs, &h_fout,
-                             &h_tok, &h_tokd[0], &h_tokd[1], &h_sums, &h_sumsd, &h_runs, &h_untok, &h_tokb, &h_tokb_runs, &h_rmd5})
+                             &h_tok, &h_tokd[0], &h_tokd[1], &h_sums, &h_sumsd, &h_runs, &h_untok, &h_tokb, &h_tokb_runs, &h_rmd5,
+                             &h_pm, &h_pmw, &h_pms, &h_pm_segs})
             b->release();
         if (abort_word) (void)hipFree(abort_word);
         if (ev_in) (void)hipEventDestroy(ev_in);
@@ -307,7 +324,8 @@ struct rsh_ctx {
             if (e) (void)hipEventDestroy(e);
         if (ev_flags) (void)hipEventDestroy(ev_flags);
         if (ev_prep) (void)hipEventDestroy(ev_prep);
-        for (hipEvent_t e : {ev_k1a, ev_k1b, ev_gen_a, ev_gen_b, ev_rs_tail, ev_tok[0], ev_tok[1], ev_sums_a, ev_sums_b})
+        for (hipEvent_t e : {ev_k1a, ev_k1b, ev_gen_a, ev_gen_b, ev_rs_tail, ev_tok[0], ev_tok[1], ev_sums_a, ev_sums_b,
+                             ev_pm, ev_pma, ev_pmb})
             if (e) (void)hipEventDestroy(e);
         if (aux) (void)hipStreamDestroy(aux);
         if (phase) (void)hipStreamDestroy(phase);

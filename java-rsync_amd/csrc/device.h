@@ -510,6 +510,16 @@ struct ChunkIndexEnt {
 hipError_t launch_chunk_index(const ChunkIndexEnt* ents, uint32_t nfiles, int32_t max_keys, hipStream_t s,
                               bool bg = false);
 
+// The phase map of a single-file scan (device_phase.hip, phase_map.h): one workgroup per sample (device-readable
+// descriptors) keys the positions [a, a + 2B) of the source, looks them up in the file's chunk index (d_kslots, kmask,
+// d_dup: launch_chunk_index) and writes the sample's PhaseAnchor record (device memory).
+struct PhaseSample;
+struct PhaseAnchor;
+hipError_t launch_phase_map(const uint8_t* d_data, int64_t n, uint32_t B, const unsigned long long* d_kslots,
+                            uint32_t kmask, const uint8_t* d_dup, const PhaseSample* samples, uint32_t nsamples,
+                            PhaseAnchor* d_out, hipStream_t s);
+hipError_t launch_warm_phase(hipStream_t s);
+
 // splitmix64 counter stream (bench input): byte i = byte (i % 8) of mix(key + (i / 8 + 1) * golden).
 hipError_t launch_fill_splitmix(uint8_t* d_out, int64_t n, uint64_t key, int64_t byte_offset, hipStream_t s);
 

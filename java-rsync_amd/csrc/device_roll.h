@@ -43,4 +43,12 @@ __device__ __forceinline__ int32_t sbyte_of(const uint32_t (&w)[4], int i) {
     return (int32_t)(int8_t)(uint8_t)(w[i >> 2] >> (8 * (i & 3)));
 }
 
+// bit i set for positions base + i in [lo, hi), i < 16
+__device__ __forceinline__ uint32_t probe_valid16(int64_t base, int64_t lo, int64_t hi) {
+    const int64_t a = lo - base, b = hi - base;
+    if (b <= 0 || a >= 16 || b <= a) return 0u;
+    const int ia = a < 0 ? 0 : (int)a, ib = b > 16 ? 16 : (int)b;
+    return (0xFFFFu >> (16 - ib)) & (0xFFFFu << ia);
+}
+
 }  // namespace rsh

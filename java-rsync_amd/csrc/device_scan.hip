@@ -138,14 +138,6 @@ __device__ __forceinline__ void probe_check16(const ScanFile& F, const ProbeTabl
     }
 }
 
-// bit i set for positions base + i in [lo, hi), i < 16
-__device__ __forceinline__ uint32_t probe_valid16(int64_t base, int64_t lo, int64_t hi) {
-    const int64_t a = lo - base, b = hi - base;
-    if (b <= 0 || a >= 16 || b <= a) return 0u;
-    const int ia = a < 0 ? 0 : (int)a, ib = b > 16 ? 16 : (int)b;
-    return (0xFFFFu >> (16 - ib)) & (0xFFFFu << ia);
-}
-
 __global__ __launch_bounds__(PROBE_THREADS) void probe_first_kernel(ProbeArgs A) {
     __builtin_amdgcn_s_setprio(3);  // resolver latency path: ahead of a co-running speculation launch
     __shared__ int32_t sh[4 * PROBE_THREADS / 64];

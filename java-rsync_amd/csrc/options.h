@@ -48,6 +48,9 @@ enum Opt : int {
                            // log2 of the stages per turn; +32: launches of any size too)
     OPT_TOKENS_RUNS_BATCH, // rsh_receiver_combine_batch_resident: run records per file and launch of the segment's token walk
     OPT_RESIDENT_MD5_BYTES,  // ... pinned staging of the verify digests' downloads (a larger file is digested piece by piece)
+    OPT_SCAN_PHASE_MAP,    // single-file scan: phase launches after which the next hint that nothing covers maps the rest of
+                           // the source (phase_map.h; 2 is the measured setting); 0, the default: never -- the map is a
+                           // bet on a scan that lives, and one that a poisoned digest ends early loses it
     OPT_COUNT
 };
 
@@ -66,6 +69,7 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"fault_inject", 0},        {"tokens_span", 256LL << 10}, {"tokens_piece", 8LL << 20},
     {"sums_piece", 32LL << 20}, {"tokens_runs", 64LL << 10}, {"k1_dma", 1},
     {"k1_prio", 1},             {"tokens_runs_batch", 4096}, {"resident_md5_bytes", 1LL << 30},
+    {"scan_phase_map", 0},
 };
 
 inline const OptInfo* opt_info() { return kOpts; }

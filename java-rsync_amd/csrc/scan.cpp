@@ -113,6 +113,7 @@ hipError_t ctx_warm(rsh_ctx* c) {
     ok(rsh::launch_warm_io(c->stream));
     ok(rsh::launch_warm_tokens(c->stream));
     ok(rsh::launch_warm_sums(c->stream));
+    ok(rsh::launch_warm_phase(c->stream));
     ok(scan_buffers_ensure(c, kC, kDl, kC, true));
     ok(prep_ensure(c, kLeadWindows + rsh::opt(rsh::OPT_SCAN_SAMPLES) + 1));
     constexpr size_t kSmall = 64 << 10;  // PinnedBuf's least allocation
@@ -268,6 +269,7 @@ int scan_device(rsh_ctx* c, const uint8_t* d_src, int64_t n, const rsh_header* h
     const int32_t C = h->chunk_count;
     const int32_t dl = h->digest_length;
     const int64_t na = (n + B - 1) / B;
+    c->last_plan.clear();  // (rsh_debug_phase_plan: the last scan's)
     if (na > 2147483647LL) return RSH_E_OVERFLOW;
     const int64_t nf = std::min<int64_t>(na, C);
     const uint32_t ns = pow2_at_least(2 * (uint64_t)C + 2);
@@ -488,6 +490,7 @@ int scan_device(rsh_ctx* c, const uint8_t* d_src, int64_t n, const rsh_header* h
     if (CallTrace::on()) fprintf(stderr, "[rsh] resolver   starts at %9.3f ms\n", ms_since(t0));
     HipBackend be(c, d_src, n, table, d_weak, seed);
     be.rs_ = rs;
+    be.map_after = rsh::opt(rsh::OPT_SCAN_PHASE_MAP);
     be.table.slots = c->slots.as<unsigned long long>();
     be.table.mask = ns - 1;
     be.aw = c->h_aw.as<int32_t>();
@@ -733,6 +736,7 @@ int scan_tiled(rsh_ctx* c, const std::function<hipError_t(uint8_t*, int64_t, int
     const int32_t C = h->chunk_count;
     const int32_t dl = h->digest_length;
     const int64_t na = (n + B - 1) / B;
+    c->last_plan.clear();  // (rsh_debug_phase_plan: the last scan's)
     if (na > 2147483647LL) return RSH_E_OVERFLOW;
     const uint32_t ns = pow2_at_least(2 * (uint64_t)C + 2);
     const int64_t T = std::max<int64_t>(16 * B, tile_bytes / B * B), H = 16 * B;

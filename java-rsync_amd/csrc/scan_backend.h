@@ -467,12 +467,17 @@ class HipBackend : public rsh::ScanBackend {
     double phase_ms = 0;  // the K1s of the phase speculations that landed
     void phase_hint(int64_t s) override {
         if (ph_s0_ >= 0 && s >= ph_s0_ && (s - ph_s0_) % B_ == 0 && s < ph_s0_ + ph_count_ * B_) return;  // covered
+        if (plan_seg(s)) return;  // ... by the plan
+        if (map_after > 0 && !pm_tried_ && ph_launches >= map_after && !tiled && err == hipSuccess) {
+            map_rest(s);
+            if (plan_seg(s) || err != hipSuccess) return;
+        }
         ensure(s);
         // windows wholly in the data the device holds: the rest of the file, or of the tile
         const int64_t hi = tiled ? std::min(n_, tile_lo + tile_T + tile_H) : n_;
         const int64_t count = hi == n_ ? (n_ - s + B_ - 1) / B_ : (hi - s - B_) / B_ + 1;
         if (count < kPhaseMinWindows || ph_launches >= kPhaseMaxLaunches || err != hipSuccess) return;
-        phase_stop();  // one at another phase is dead work now
+        phase_stop_single();  // one at another phase is dead work now
         CallTrace tr("phase_spec", s);
         ph_gen_ = c_->next_gen();
         hipStream_t ps = c_->phase;  // its own stream: it does not queue behind a prefix speculation on aux
@@ -503,7 +508,7 @@ class HipBackend : public rsh::ScanBackend {
     }
     bool phase_sums(int64_t s, bool wait, rsh::PhaseView* v) override {
         if (ph_s0_ < 0 || s < ph_s0_ || (s - ph_s0_) % B_ != 0 || s >= ph_s0_ + ph_count_ * B_ || err != hipSuccess)
-            return false;
+            return plan_sums(s, wait, v);
         if (!ph_landed_) {
             // a phase K1 that has finished leaves only its sums' download (~1 MB): waiting for it beats a host
             // digest of the window (0.13 ms at B = 128 KiB), the resolver's alternative at a hit
@@ -539,6 +544,16 @@ class HipBackend : public rsh::ScanBackend {
     // A phase speculation still running when the scan ends (or moves to another phase) is stopped; later
     // work on the context stream waits until its waves have left.
     void phase_stop() {
+        phase_stop_single();
+        if (pm_launched_ && !pm_landed_ && hipEventQuery(c_->ev_pm) == hipErrorNotReady) {
+            ok(hipStreamWriteValue32(rs_, c_->abort_word + rsh_ctx::kPlanWord, (uint32_t)pm_gen_, 0));
+            ok(hipStreamWaitEvent(rs_, c_->ev_pm, 0));
+            if (rs_ != c_->stream) ok(hipStreamWaitEvent(c_->stream, c_->ev_pm, 0));
+        }
+        pm_launched_ = false;
+        plan_.clear();
+    }
+    void phase_stop_single() {
         if (ph_s0_ >= 0 && !ph_landed_ && hipEventQuery(c_->ev_phase[ph_set_]) == hipErrorNotReady) {
             ok(hipStreamWriteValue32(rs_, c_->abort_word + rsh_ctx::kPhaseWord, (uint32_t)ph_gen_, 0));
             ok(hipStreamWaitEvent(rs_, c_->ev_phase[ph_set_], 0));
@@ -549,9 +564,175 @@ class HipBackend : public rsh::ScanBackend {
         ph_landed_ = false;
     }
 
+    // ---- the phase map (phase_map.h): once map_after phase launches have gone out, the next hint that nothing covers
+    // maps the rest of the source -- two rounds of phase_map_kernel on the round trips' queue, each waited for -- and
+    // the planner's stretches go out as one segmented K1 launch on the phase stream, into buffers, an abort word and
+    // an event of the plan's own.  phase_sums then serves a view per stretch.  One plan per scan; a scan whose map
+    // finds nothing (or whose shape the segmented kernel does not take) goes on as before. ----
+    int64_t map_after = 0;  // option scan_phase_map for this scan (scan_device sets it; 0: never)
+    void map_rest(int64_t s) {
+        pm_tried_ = true;
+        const int64_t C = t_.chunk_count, rest = (n_ - s) / B_, na_all = (n_ + B_ - 1) / B_;
+        hipDeviceptr_t alo = nullptr;
+        size_t asz = 0;
+        if (rest < 2 * kPhaseMinWindows || C < 2 || B_ % 128 != 0 || (B_ >> 7) < 4 || (B_ >> 7) > 1024) return;
+        if (hipMemGetAddressRange(&alo, &asz, reinterpret_cast<hipDeviceptr_t>(const_cast<uint8_t*>(x_))) != hipSuccess) {
+            (void)hipGetLastError();
+            return;
+        }
+        CallTrace tr("phase_map", s);
+        ok(hipEventSynchronize(c_->ev_pm));  // an earlier scan's plan launch has left the plan's buffers
+        std::vector<rsh::PhaseSample> sa, sb;
+        rsh::phase_round_a(s, n_, B_, &sa);
+        const int64_t cap_s = (int64_t)sa.size() + rest + 1;
+        const uint32_t ns = pow2_at_least(4 * (uint64_t)C + 2);  // load factor <= 1/4: most keys miss at their first slot
+        constexpr size_t kEntAt = 64;                            // h_pm: the index descriptor, the samples, the anchors
+        ok(c_->pm_index.ensure((size_t)ns * 8 + (size_t)C + 8));
+        ok(c_->pm_anchor.ensure((size_t)cap_s * sizeof(rsh::PhaseAnchor)));
+        ok(c_->h_pm.ensure(kEntAt + (size_t)cap_s * (sizeof(rsh::PhaseSample) + sizeof(rsh::PhaseAnchor))));
+        if (err != hipSuccess) return;
+        auto* slots = c_->pm_index.as<unsigned long long>();
+        uint8_t* dup = reinterpret_cast<uint8_t*>(slots + ns);
+        auto* ent = c_->h_pm.as<rsh::ChunkIndexEnt>();
+        auto* hs = reinterpret_cast<rsh::PhaseSample*>(c_->h_pm.as<uint8_t>() + kEntAt);
+        auto* ha = reinterpret_cast<rsh::PhaseAnchor*>(hs + cap_s);
+        auto* da = c_->pm_anchor.as<rsh::PhaseAnchor>();
+        *ent = rsh::ChunkIndexEnt{rsh::TableEnt{slots, d_table_weak_, ns - 1, (int32_t)C}, dup};
+        ok(hipMemsetAsync(slots, 0, (size_t)ns * 8 + (size_t)C, rs_));
+        ok(rsh::launch_chunk_index(ent, 1, (int32_t)C, rs_));
+        // a round: samples [i0, i0 + cnt) of hs through the kernel, their records down by the copy kernel
+        auto round = [&](int64_t i0, int64_t cnt) {
+            if (cnt <= 0 || err != hipSuccess) return;
+            ok(rsh::launch_phase_map(x_, n_, (uint32_t)B_, slots, ns - 1, dup, hs + i0, (uint32_t)cnt, da + i0, rs_));
+            ok(copy_to_host({rsh::CopyEnt{reinterpret_cast<const uint8_t*>(da + i0), reinterpret_cast<uint8_t*>(ha + i0),
+                                          cnt * (int64_t)sizeof(rsh::PhaseAnchor)}},
+                            rs_));
+            ok(hipStreamSynchronize(rs_));
+            for (int64_t i = i0; i < i0 + cnt; ++i) bytes_read += rsh::phase_sample_end(hs[i].a, n_, B_) - hs[i].a + B_;
+        };
+        const int64_t nsa = (int64_t)sa.size();
+        if (nsa > 0) memcpy(hs, sa.data(), (size_t)nsa * sizeof(rsh::PhaseSample));
+        round(0, nsa);
+        if (err != hipSuccess) return;
+        rsh::phase_round_b(hs, ha, nsa, n_, B_, na_all, &sb);
+        const int64_t nsb = std::min<int64_t>((int64_t)sb.size(), cap_s - nsa);
+        if (nsb > 0) memcpy(hs + nsa, sb.data(), (size_t)nsb * sizeof(rsh::PhaseSample));
+        round(nsa, nsb);
+        if (err != hipSuccess) return;
+        // both rounds in ascending order of position
+        std::vector<int64_t> order((size_t)(nsa + nsb));
+        for (size_t i = 0; i < order.size(); ++i) order[i] = (int64_t)i;
+        std::inplace_merge(order.begin(), order.begin() + nsa, order.end(),
+                           [&](int64_t x, int64_t y) { return hs[x].a < hs[y].a; });
+        std::vector<rsh::PhaseSample> ms(order.size());
+        std::vector<rsh::PhaseAnchor> ma(order.size());
+        for (size_t i = 0; i < order.size(); ++i) {
+            ms[i] = hs[order[i]];
+            ma[i] = ha[order[i]];
+        }
+        std::vector<rsh::PhaseSeg> segs;
+        rsh::phase_plan(ms.data(), ma.data(), (int64_t)ms.size(), s, n_, B_, C, kPhaseMinWindows, &segs);
+        if (segs.empty()) return;
+        // the plan's K1: a K1Seg wave per 64 full windows of a stretch whose lines lie in the source's allocation
+        // (seg_plan's rule, scan.cpp), the leftovers as K1Tail entries, the full-length ones first
+        const uintptr_t addr = reinterpret_cast<uintptr_t>(x_), a_lo = reinterpret_cast<uintptr_t>(alo), a_hi = a_lo + asz;
+        int64_t total = 0, nseg = 0, ntail = 0;
+        std::vector<rsh_ctx::PlanSeg> plan;
+        for (const rsh::PhaseSeg& g : segs) {
+            const uint32_t a1 = (uint32_t)((addr + (uintptr_t)g.s0) % 128);
+            int64_t waves = std::min(g.count, (n_ - g.s0) / B_) / 64;
+            if (addr + (uintptr_t)g.s0 - a1 < a_lo) waves = 0;
+            while (waves > 0 && addr + (uintptr_t)g.s0 - a1 + (uintptr_t)(waves * 64 * B_) + 128 > a_hi) --waves;
+            plan.push_back(rsh_ctx::PlanSeg{g, total, waves});
+            total += g.count;
+            nseg += waves;
+            ntail += g.count - 64 * waves;
+        }
+        const size_t bytes = (size_t)nseg * sizeof(rsh::K1Seg) + (size_t)ntail * sizeof(rsh::K1Tail);
+        ok(c_->pm_weak.ensure((size_t)total * 4));
+        ok(c_->pm_strong.ensure((size_t)total * dl_ + 1));
+        ok(c_->h_pmw.ensure((size_t)total * 4));
+        ok(c_->h_pms.ensure((size_t)total * dl_ + 1));
+        ok(c_->pm_segs.ensure(bytes));
+        ok(c_->h_pm_segs.ensure(bytes));
+        if (err != hipSuccess) return;
+        pm_gen_ = c_->next_gen();
+        int32_t* dw = c_->pm_weak.as<int32_t>();
+        uint8_t* dst = c_->pm_strong.as<uint8_t>();
+        auto* sg = c_->h_pm_segs.as<rsh::K1Seg>();
+        auto* tl = reinterpret_cast<rsh::K1Tail*>(sg + nseg);
+        rsh::K1Tail* te = tl;
+        for (const rsh_ctx::PlanSeg& q : plan) {
+            const uint32_t a1 = (uint32_t)((addr + (uintptr_t)q.g.s0) % 128);
+            for (int64_t v = 0; v < q.waves; ++v)
+                *sg++ = rsh::K1Seg{x_ + q.g.s0 - a1 + v * 64 * B_, dw + q.off + v * 64, dst + (q.off + v * 64) * dl_,
+                                   c_->abort_word + rsh_ctx::kPlanWord, pm_gen_, a1};
+            for (int64_t k = 64 * q.waves; k < q.g.count; ++k)
+                *te++ = rsh::K1Tail{x_ + q.g.s0, n_ - q.g.s0, dw + q.off, dst + q.off * dl_, (uint32_t)k};
+        }
+        const uint32_t nfull =
+            (uint32_t)(std::stable_partition(tl, te, [&](const rsh::K1Tail& t) { return (int64_t)(t.c + 1) * B_ <= t.n; }) - tl);
+        phase_stop_single();  // a launch at another phase is dead work now
+        hipStream_t ps = c_->phase;
+        ok(hipStreamWaitEvent(ps, c_->ev_in, 0));
+        ok(copy_to_host({rsh::CopyEnt{c_->h_pm_segs.as<uint8_t>(), c_->pm_segs.as<uint8_t>(), (int64_t)bytes}}, ps));
+        c_->pm_timed = false;
+        ok(hipEventRecord(c_->ev_pma, ps));
+        ok(rsh::launch_block_sums_segments(
+            c_->pm_segs.as<rsh::K1Seg>(), (uint32_t)nseg,
+            reinterpret_cast<const rsh::K1Tail*>(c_->pm_segs.as<uint8_t>() + (size_t)nseg * sizeof(rsh::K1Seg)),
+            (uint32_t)ntail, nfull, (uint32_t)B_, (uint32_t)dl_, seed_word(seed_), ps));
+        ok(hipEventRecord(c_->ev_pmb, ps));
+        ok(copy_to_host({rsh::CopyEnt{c_->pm_weak.as<uint8_t>(), c_->h_pmw.as<uint8_t>(), total * 4},
+                         rsh::CopyEnt{c_->pm_strong.as<uint8_t>(), c_->h_pms.as<uint8_t>(), total * dl_}},
+                        ps));
+        ok(hipEventRecord(c_->ev_pm, ps));
+        if (err != hipSuccess) return;
+        plan_.swap(plan);
+        c_->last_plan = plan_;
+        pm_total_ = total;
+        pm_launched_ = true;
+        pm_landed_ = false;
+        ++ph_launches;
+    }
+    // the plan's stretch that holds s at its phase
+    const rsh_ctx::PlanSeg* plan_seg(int64_t s) const {
+        auto it = std::upper_bound(plan_.begin(), plan_.end(), s,
+                                   [](int64_t v, const rsh_ctx::PlanSeg& q) { return v < q.g.s0; });
+        if (it == plan_.begin()) return nullptr;
+        --it;
+        return (s - it->g.s0) % B_ == 0 && s < it->g.s0 + it->g.count * B_ ? &*it : nullptr;
+    }
+    bool plan_sums(int64_t s, bool wait, rsh::PhaseView* v) {
+        const rsh_ctx::PlanSeg* q = err == hipSuccess ? plan_seg(s) : nullptr;
+        if (!q) return false;
+        if (!pm_landed_) {  // (as a single launch's: wait for a finished K1's download, else only ask)
+            if (wait || hipEventQuery(c_->ev_pmb) == hipSuccess) {
+                CallTrace tr("plan_wait", s);
+                ok(hipEventSynchronize(c_->ev_pm));
+                pm_landed_ = err == hipSuccess;
+            } else {
+                pm_landed_ = hipEventQuery(c_->ev_pm) == hipSuccess;
+            }
+            if (!pm_landed_) return false;
+            bytes_read += pm_total_ * B_;
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, c_->ev_pma, c_->ev_pmb) == hipSuccess) phase_ms += ms;
+        }
+        v->s0 = q->g.s0;
+        v->count = q->g.count;
+        v->w = c_->h_pmw.as<int32_t>() + q->off;
+        v->st = c_->h_pms.as<uint8_t>() + q->off * dl_;
+        return true;
+    }
+
   private:
+    std::vector<rsh_ctx::PlanSeg> plan_;  // ascending, disjoint
+    bool pm_tried_ = false, pm_launched_ = false, pm_landed_ = false;
+    int pm_gen_ = 0;
+    int64_t pm_total_ = 0;
     static constexpr int64_t kPhaseMinWindows = 8;    // shorter remainders resolve faster on the generic path
-    static constexpr int64_t kPhaseMaxLaunches = 64;  // each covers the rest of the file
+    static constexpr int64_t kPhaseMaxLaunches = 64;  // a single launch covers the rest of the file
     int64_t ph_s0_ = -1, ph_count_ = 0;
     int ph_gen_ = 0;
     int ph_set_ = 0;  // the buffer set (rsh_ctx::ph_weak[i] ...) of the current phase launch

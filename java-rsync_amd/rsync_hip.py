@@ -211,7 +211,8 @@ DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_rese
                  "rsh_debug_streams_busy", "rsh_debug_kernel_ms", "rsh_debug_multi_selftest", "rsh_debug_generation",
                  "rsh_debug_tokens_selftest", "rsh_debug_sums_selftest", "rsh_debug_tokens_scan_selftest",
                  "rsh_debug_untokens_selftest", "rsh_debug_k1_dma_swizzle", "rsh_debug_k1_wave_times",
-                 "rsh_debug_tokens_scan_batch_selftest"]
+                 "rsh_debug_tokens_scan_batch_selftest", "rsh_debug_phase_plan", "rsh_debug_phase_map_selftest",
+                 "rsh_debug_phase_round_b", "rsh_debug_phase_segments"]
 
 _LIB = None
 
@@ -340,8 +341,14 @@ def lib():
         "rsh_tokens_frame_batch_device": ([P, ctypes.POINTER(TokenFrameJob), I32], ctypes.c_int),
         "rsh_receiver_combine_batch_resident": ([P, ctypes.POINTER(ResidentJob), I32, I32], ctypes.c_int),
         "rsh_debug_tokens_scan_batch_selftest": ([P, ctypes.POINTER(TokenScanJob), I32, P, I32, I32], ctypes.c_int),
+        "rsh_debug_phase_plan": ([P, P, I64, ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_debug_phase_map_selftest": ([P, P, I64, I32, P, I32, P, I64, I32, P, P], ctypes.c_int),
+        "rsh_debug_phase_round_b": ([P, P, I64, I64, I32, I64, P, I64, ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_debug_phase_segments": ([P, P, I64, I64, I64, I32, I32, I64, P, I64, ctypes.POINTER(I64)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
+        if os.environ.get("RSH_LIB") and name in DEBUG_EXPORTS and not hasattr(L, name):
+            continue  # an older commit's library in an A/B run: it lacks the newer diagnostics
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res
@@ -575,6 +582,49 @@ def sums_selftest(h, weak=None, strong=None, wire=None, span=0, unframe=False):
     return nd.value
 
 
+# rsh_phase_anchor / rsh_phase_seg (include/rsync_hip_debug.h)
+PHASE_NONE, PHASE_FOUND, PHASE_OVERFLOW = 0, 1, 2
+PHASE_ANCHOR_DTYPE = np.dtype([("p", "<i8"), ("i", "<i4"), ("status", "<i4")])
+PHASE_SEG_DTYPE = np.dtype([("s0", "<i8"), ("count", "<i8"), ("pref0", "<i8"), ("waves", "<i8")])
+
+
+def phase_map_selftest(src, block_length, weak, samples, ctx=None, base_offset=0):
+    """rsh_debug_phase_map_selftest: the phase map's records (PHASE_ANCHOR_DTYPE) for the sample positions `samples`
+    over the host source `src` and the table's weak sums, from the kernel's host stand-in; with a Context, the pair
+    (stand-in's records, phase_map_kernel's records), the source placed base_offset bytes past a 256-byte boundary."""
+    x = _u8(src)
+    w = np.ascontiguousarray(weak, np.int32)
+    a = np.ascontiguousarray(samples, np.int64)
+    host = np.zeros(a.size, PHASE_ANCHOR_DTYPE)
+    dev = np.zeros(a.size, PHASE_ANCHOR_DTYPE)
+    _check(lib().rsh_debug_phase_map_selftest(None if ctx is None else ctx.handle, _ptr(x), x.size, block_length,
+                                              _ptr(w), w.size, _ptr(a), a.size, base_offset, _ptr(host),
+                                              None if ctx is None else _ptr(dev)))
+    return host if ctx is None else (host, dev)
+
+
+def phase_round_b(samples, anchors, n, block_length, cap):
+    """rsh_debug_phase_round_b: the second round's sample positions from the first round's samples and records."""
+    a = np.ascontiguousarray(samples, np.int64)
+    an = np.ascontiguousarray(anchors, PHASE_ANCHOR_DTYPE)
+    out = np.zeros(max(1, n // max(block_length, 1) + 2), np.int64)
+    k = ctypes.c_int64()
+    _check(lib().rsh_debug_phase_round_b(_ptr(a), _ptr(an), a.size, n, block_length, cap, _ptr(out), out.size,
+                                         ctypes.byref(k)))
+    return out[:k.value].copy()
+
+
+def phase_segments(samples, anchors, lo, n, block_length, chunk_count, min_windows=8):
+    """rsh_debug_phase_segments: the plan [(s0, count, pref0)] from both rounds' samples in ascending order."""
+    a = np.ascontiguousarray(samples, np.int64)
+    an = np.ascontiguousarray(anchors, PHASE_ANCHOR_DTYPE)
+    segs = np.zeros(a.size + 1, PHASE_SEG_DTYPE)
+    k = ctypes.c_int64()
+    _check(lib().rsh_debug_phase_segments(_ptr(a), _ptr(an), a.size, lo, n, block_length, chunk_count, min_windows,
+                                          _ptr(segs), segs.size, ctypes.byref(k)))
+    return [(int(g["s0"]), int(g["count"]), int(g["pref0"])) for g in segs[:k.value]]
+
+
 def set_option(name, value):
     """A library tunable or diagnostic switch (include/rsync_hip_debug.h; tests and A/B runs only)."""
     _check(lib().rsh_debug_set_option(name.encode(), int(value)))
@@ -640,10 +690,21 @@ class Context:
         return self._p
 
     def kernel_ms(self, which):
-        """The last Generator (0) or speculation (1) K1's duration from its own dispatch events (-1: not timed)."""
+        """The last Generator (0) or speculation (1) K1's duration from its own dispatch events, the last sums kernel's
+        (2) or the last phase_map_selftest's kernel launch (3) from events around it (-1: not timed)."""
         ms = ctypes.c_double(-1.0)
         _check(lib().rsh_debug_kernel_ms(self._p, which, ctypes.byref(ms)))
         return ms.value
+
+    def phase_plan(self):
+        """rsh_debug_phase_plan: the last single-file scan's plan, [(s0, count, pref0, waves)] (empty: no plan)."""
+        k = ctypes.c_int64()
+        rc = lib().rsh_debug_phase_plan(self._p, None, 0, ctypes.byref(k))
+        if rc not in (RSH_OK, RSH_E_NOSPACE):
+            _check(rc)
+        segs = np.zeros(max(1, k.value), PHASE_SEG_DTYPE)
+        _check(lib().rsh_debug_phase_plan(self._p, _ptr(segs), segs.size, ctypes.byref(k)))
+        return [(int(g["s0"]), int(g["count"]), int(g["pref0"]), int(g["waves"])) for g in segs[:k.value]]
 
     def generation(self, set_to=-1):
         """The context's launch generation, after setting it to set_to when >= 0 (rsh_debug_generation)."""
