@@ -45,7 +45,9 @@ extern "C" {
 #define RSH_E_NOSOURCE (-10) /* the context holds no source from its last scan (tiled, trimmed, or reused since) */
 
 /* Checksum.Header; wire order of Connection.sendChecksumHeader (Connection.java:40-45) is
- * chunk_count, block_length, digest_length, remainder (4 x little-endian int32). */
+ * chunk_count, block_length, digest_length, remainder (4 x little-endian int32).
+ * Any 0 < block_length <= 131072 is legal (Checksum.java:75-92) and gives the same results; block lengths from 512 up
+ * run on the coalesced kernels, multiples of 128 or not ("Block lengths a peer may send"). */
 typedef struct {
     int32_t chunk_count;
     int32_t block_length;

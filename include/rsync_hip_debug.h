@@ -8,7 +8,11 @@
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
  * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio, tokens_runs_batch, resident_md5_bytes,
- * scan_phase_map.
+ * scan_phase_map, k1_anyb.
+ *
+ * k1_anyb = 1 (default): block lengths of 512 and more that are no multiple of 128 take the coalesced any-B K1 (whole
+ * 128-byte lines, one ring offset per chunk, abortable, timed), in single-file and batched launches; 0: every chunk of
+ * such a file on one lane (the A/B partner and the tests' cross-check, from one library).
  *
  * k1_dma = 1 (default): the main waves of the pipelined K1 stream their stages from HBM straight into LDS wherever
  * every wave's base is 16-B aligned; 0: the register-staged form at every base (the A/B partner, from one library).
@@ -44,8 +48,27 @@ void rsh_debug_reset_options(void);
  * which 0 = the last rsh_block_sums_device's K1 (the Generator), 1 = the last single-file scan's aligned speculation
  * when it ran to completion, 2 = the last sums_frame_kernel / sums_unframe_kernel launch (HIP events around it),
  * 3 = the phase_map_kernel launch of the last rsh_debug_phase_map_selftest with a context (HIP events around it).
- * *ms = -1 when that launch was not timed (a shape whose kernel takes no events). */
+ * *ms = -1 when that launch was not timed: for which = 0, a shape with no coalesced wave (block lengths below 512, files
+ * of fewer than 64 full chunks, k1_anyb = 0 at a block length off a multiple of 128) -- the per-lane kernel takes no
+ * events. */
 int rsh_debug_kernel_ms(rsh_ctx* ctx, int32_t which, double* ms);
+
+/* Which K1 form a launch takes, without a device: the launchers' own decision (k1_plan.h) over a made-up address.
+ * addr: the data's address; alloc_lo / alloc_size: its allocation (size 0: unknown -- only [addr, addr + n) is
+ * readable); the options are read as they stand.  main_waves: coalesced waves of 64 chunks in `form`; gathered_chunks:
+ * full-length leftovers in gathered coalesced waves; lane_chunks: chunks one per lane.  The three always add up to the
+ * file's chunks. */
+typedef struct {
+    int32_t form;         /* 0 per lane, 1 pipelined (direct-to-LDS), 2 pipelined (register-staged), 3 shift, 4 any-B */
+    int32_t align_class;  /* 16, 8, 4 or 1: the widest of them that divides the address and the block length */
+    uint32_t main_waves, gathered_chunks, lane_chunks;
+} rsh_k1_plan;
+int rsh_debug_k1_plan(uint64_t addr, uint64_t alloc_lo, uint64_t alloc_size, int64_t n, int32_t block_length,
+                      rsh_k1_plan* out);
+/* The batched planner over nfiles shapes, one record per file.  [lo[i], hi[i]): the readable bytes around file i (lo or
+ * hi NULL, or lo[i] == hi[i]: the file's own bytes). */
+int rsh_debug_k1_plan_batch(const uint64_t* addr, const uint64_t* lo, const uint64_t* hi, const int64_t* n,
+                            const int32_t* block_length, int32_t nfiles, rsh_k1_plan* out);
 
 /* The context's launch generation (the abort and hit-map words' values): *gen its current value; set >= 0 (at most
  * the wrap point, 0x7FFFFF00) sets it first -- tests take a context across the wrap, where the device drains and every

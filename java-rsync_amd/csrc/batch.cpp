@@ -56,9 +56,10 @@ struct K1Set {
     std::vector<K1Lane> lanes;
     int lane_align = 16;
     bool partial = tail_gather_on();
+    bool anyb = false;  // some group is at B % 128 != 0
     uint32_t ngroups = 0;
     void plan(const std::vector<K1File>& kf) {
-        ngroups = plan_block_sums_files(kf.data(), (int32_t)kf.size(), &plans, &lanes, &lane_align, &partial);
+        ngroups = plan_block_sums_files(kf.data(), (int32_t)kf.size(), &plans, &lanes, &lane_align, &partial, &anyb);
     }
 };
 
@@ -161,7 +162,8 @@ hipError_t SegmentLayout::plan(BatchState* S, const std::vector<FileLayout*>& fi
     auto k1_file = [&](const FileLayout& fs, int64_t w0, int64_t w1) {
         return K1File{fs.d_src + w0 * fs.B, std::min<int64_t>(fs.n, w1 * fs.B) - w0 * fs.B, (uint32_t)fs.B, (uint32_t)fs.dl,
                       (uint32_t)(w1 - w0), S->src_weak.as<int32_t>() + fs.off_na + w0,
-                      S->src_strong.as<uint8_t>() + fs.off_as + w0 * fs.dl};
+                      S->src_strong.as<uint8_t>() + fs.off_as + w0 * fs.dl,
+                      fs.d_src, fs.d_src + fs.n};  // (any-B groups: the lines around a window range lie in the file)
     };
     std::vector<K1File> k1;
     for (const FileLayout* fs : file) k1.push_back(k1_file(*fs, 0, fs->na));
@@ -498,7 +500,7 @@ int Scan::launch_spec_k1() {
     RSH_BHIP(hipStreamWaitEvent(aux, L.chain_on ? c->ev_in : c->ev_prep, 0));
     RSH_BHIP(launch_block_sums_batch(S->spec_k1.groups.as<K1Group>(), k.ngroups, S->spec_k1.lanes.as<K1Lane>(),
                                      (uint32_t)k.lanes.size(), k.lane_align, seed_word(seed), aux, c->abort_word, gen,
-                                     k.partial));
+                                     k.partial, k.anyb));
     return RSH_OK;
 }
 
@@ -676,7 +678,7 @@ int Scan::walk_phase0() {
     RSH_BHIP(stage_k1(S->spec_k1, {&L.a, &L.b}, aux));
     RSH_BHIP(hipStreamWaitEvent(aux, c->ev_in, 0));  // the sources only (no lead check in chain mode)
     RSH_BHIP(launch_block_sums_batch(k.groups.as<K1Group>(), L.a.ngroups, k.lanes.as<K1Lane>(), (uint32_t)L.a.lanes.size(),
-                                     L.a.lane_align, seed_word(seed), aux, c->abort_word, gen, L.a.partial));
+                                     L.a.lane_align, seed_word(seed), aux, c->abort_word, gen, L.a.partial, L.a.anyb));
     RSH_BHIP(hipStreamWaitEvent(aux, c->ev_in, 0));  // the flags need the received tables
     FlagEnt* fa = S->h_flagents_a.as<FlagEnt>();
     uint32_t max_na = 0;
@@ -716,7 +718,7 @@ int Scan::walk_phase0() {
         RSH_BHIP(hipStreamWaitEvent(aux, S->ev_wa, 0));
         RSH_BHIP(launch_block_sums_batch(k.groups.as<K1Group>() + L.a.ngroups, L.b.ngroups,
                                          k.lanes.as<K1Lane>() + L.a.lanes.size(), (uint32_t)L.b.lanes.size(), L.b.lane_align,
-                                         seed_word(seed), aux, c->abort_word, gen_b, L.b.partial));
+                                         seed_word(seed), aux, c->abort_word, gen_b, L.b.partial, L.b.anyb));
         k1_launched = true;
     }
     if (trace)
@@ -1082,7 +1084,7 @@ int block_sums_batch_claimed(rsh_ctx* ctx, const rsh_block_job* jobs, int32_t nj
     RSH_BHIP(stage_k1(S->gen_k1, {&k}, ctx->stream));
     RSH_BHIP(launch_block_sums_batch(S->gen_k1.groups.as<K1Group>(), k.ngroups, S->gen_k1.lanes.as<K1Lane>(),
                                      (uint32_t)k.lanes.size(), k.lane_align, seed_word(seed), ctx->stream, nullptr, 0,
-                                     k.partial));
+                                     k.partial, k.anyb));
     return RSH_OK;
 }
 

@@ -548,6 +548,51 @@ int32_t rsh_debug_k1_dma_swizzle(int32_t what, int32_t chunk, int32_t index) {
     return (int32_t)(what == 0 ? rsh::k1_dma_piece(c, i) : what == 1 ? rsh::k1_dma_slot(c, i) : rsh::k1_dma_lds_byte(c, i));
 }
 
+int rsh_debug_k1_plan(uint64_t addr, uint64_t alloc_lo, uint64_t alloc_size, int64_t n, int32_t block_length,
+                      rsh_k1_plan* out) {
+    if (!out || n <= 0 || block_length <= 0 || block_length > kMaxBlockLength) return RSH_E_INVAL;
+    const int64_t C = (n + block_length - 1) / block_length;
+    if (C > 2147483647LL) return RSH_E_OVERFLOW;
+    const rsh::K1Single p = rsh::k1_plan_single(addr, alloc_lo, alloc_size, n, (uint32_t)block_length, (uint32_t)C, true,
+                                                rsh::k1_plan_opts());
+    *out = rsh_k1_plan{p.form, p.align_class, p.main_waves, p.gathered, p.lane};
+    return RSH_OK;
+}
+
+int rsh_debug_k1_plan_batch(const uint64_t* addr, const uint64_t* lo, const uint64_t* hi, const int64_t* n,
+                            const int32_t* block_length, int32_t nfiles, rsh_k1_plan* out) {
+    if (nfiles < 0 || (nfiles > 0 && (!addr || !n || !block_length || !out))) return RSH_E_INVAL;
+    std::vector<rsh::K1File> files;
+    for (int32_t i = 0; i < nfiles; ++i) {
+        if (n[i] <= 0 || block_length[i] <= 0 || block_length[i] > kMaxBlockLength) return RSH_E_INVAL;
+        const int64_t C = (n[i] + block_length[i] - 1) / block_length[i];
+        if (C > 2147483647LL) return RSH_E_OVERFLOW;
+        // (the planner reads the pointers' values only)
+        rsh::K1File f{reinterpret_cast<const uint8_t*>((uintptr_t)addr[i]), n[i], (uint32_t)block_length[i], 16u, (uint32_t)C,
+                      nullptr, nullptr};
+        if (lo && hi) {
+            f.lo = reinterpret_cast<const uint8_t*>((uintptr_t)lo[i]);
+            f.hi = reinterpret_cast<const uint8_t*>((uintptr_t)hi[i]);
+        }
+        files.push_back(f);
+        out[i] = rsh_k1_plan{0, rsh::k1_align_class(addr[i], (uint32_t)block_length[i]), 0, 0, (uint32_t)C};
+    }
+    std::vector<rsh::K1Plan> plans;
+    std::vector<rsh::K1Lane> lanes;
+    int lane_align = 16;
+    bool partial = rsh::tail_gather_on();
+    rsh::plan_block_sums_files(files.data(), nfiles, &plans, &lanes, &lane_align, &partial);
+    const rsh::K1PlanOpts po = rsh::k1_plan_opts();
+    for (const rsh::K1Plan& pl : plans) {
+        rsh_k1_plan& r = out[pl.file];
+        r.form = (pl.B % 128) != 0 ? rsh::K1_FORM_ANYB : po.dma ? rsh::K1_FORM_PIPE_DMA : rsh::K1_FORM_PIPE_REG;
+        r.main_waves = pl.nfull / 64;
+        r.gathered_chunks = pl.nfull % 64;
+        r.lane_chunks -= pl.nfull;
+    }
+    return RSH_OK;
+}
+
 int rsh_debug_kernel_ms(rsh_ctx* ctx, int32_t which, double* ms) {
     if (!ctx || !ms || which < 0 || which > 3) return RSH_E_INVAL;
     *ms = -1.0;

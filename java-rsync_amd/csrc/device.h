@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "hit_cache.h"
+#include "k1_plan.h"
 #include "rsync_hip.h"
 
 namespace rsh {
@@ -19,8 +20,8 @@ hipError_t launch_block_sums(const uint8_t* d_data, int64_t n, uint32_t B, uint3
                              const int* abort_flag = nullptr, int abort_gen = 0);
 // Timing of the next K1 launch_block_sums makes on this thread: its dispatch records start / stop in these events
 // (hipExtLaunchKernelGGL: the kernel's own timestamps, no marker packets in the stream and so no bubble before or
-// after the kernel).  k1_timing_taken() says whether that launch took them (the pipelined and the shift kernels do;
-// the rare per-lane and coalesced shapes do not, and the events then stay unrecorded).
+// after the kernel).  k1_timing_taken() says whether that launch took them (the pipelined, the shift and the any-B kernels
+// do; the per-lane shapes do not, and the events then stay unrecorded).
 void k1_timing_next(hipEvent_t start, hipEvent_t stop);
 bool k1_timing_taken();
 
@@ -37,12 +38,17 @@ hipError_t launch_block_sums_variant(int variant, const uint8_t* d_data, int64_t
 // pipelined coalesced K1 (K1Group: 64 full-length chunks, B % 128 == 0, 512 <= B <= 128 KiB, 16-B aligned
 // data) and one lane per chunk for the rest (K1Lane: the file's tail group, or every chunk of a file
 // whose shape the coalesced kernel does not take).  The descriptors must be device-readable.
+// Files at B % 128 != 0 (512 and up; option k1_anyb) are cut into groups too, for the any-B wave (anyb_wave), which
+// reads the whole 128-B lines around a group's bytes: a group is cut only where those lines lie in [lo, hi), the
+// readable bytes around the file that its caller knows of (nullptr: the file's own bytes).
 struct K1File {
     const uint8_t* data;
     int64_t n;
     uint32_t B, dl, nchunks;
     int32_t* weak;
     uint8_t* strong;
+    const uint8_t* lo = nullptr;  // readable bounds around the data (its buffer), for the any-B groups
+    const uint8_t* hi = nullptr;
 };
 struct K1Group {
     const uint8_t* data;  // chunk 0 of the group
@@ -84,7 +90,7 @@ struct K1Tail {
 hipError_t launch_block_sums_segments(const K1Seg* d_segs, uint32_t nseg, const K1Tail* d_tails, uint32_t ntail,
                                       uint32_t nfull, uint32_t B, uint32_t dl, uint32_t seed_word, hipStream_t s);
 void plan_block_sums_batch(const K1File* files, int32_t nfiles, std::vector<K1Group>* groups,
-                           std::vector<K1Lane>* lanes, int* lane_align);
+                           std::vector<K1Lane>* lanes, int* lane_align, bool* anyb = nullptr);
 // Device-side group expansion: the host plans per file (K1Plan: the file's first group index g0 and its
 // count of full 64-chunk groups) and one thread per group writes its K1Group (expand_groups_kernel), instead of
 // the host building and uploading ~40 B per 64 chunks (config 4: 32768 groups, 1.5 MB, ~0.14 ms of host time
@@ -94,16 +100,20 @@ struct K1Plan {
     int32_t* weak;
     uint8_t* strong;
     uint32_t B, dl;
-    uint32_t g0, ng;            // groups [g0, g0 + ng) of the launch are this file's chunks [0, min(64 ng, nfull))
+    uint32_t g0, ng;            // groups [g0, g0 + ng) of the launch are this file's chunks [c0, c0 + min(64 ng, nfull))
     const int* abort = nullptr;  // K1Group::abort of its groups
     int32_t file = 0;
     uint32_t nfull = 0;          // its full-length chunks covered by groups (the last group may be partial)
+    uint32_t c0 = 0;             // the first group's first chunk (64 when an any-B file's wave 0 runs per lane)
 };
 // plans (one per file with groups, ascending g0) and the host lanes; returns the total group count.  A file's
 // full-length chunks past its last full wave form a partial group (K1Group::count < 64) when *partial is set
-// on entry (option k1_gather); on return *partial says whether any plan has one.
+// on entry (option k1_gather); on return *partial says whether any plan has one.  *anyb: some group is at
+// B % 128 != 0 (launch_block_sums_batch then takes the kernel that holds the any-B wave).
 uint32_t plan_block_sums_files(const K1File* files, int32_t nfiles, std::vector<K1Plan>* plans,
-                               std::vector<K1Lane>* lanes, int* lane_align, bool* partial = nullptr);
+                               std::vector<K1Lane>* lanes, int* lane_align, bool* partial = nullptr,
+                               bool* anyb = nullptr);
+K1PlanOpts k1_plan_opts();  // the options k1_plan.h's decisions read, as they stand
 hipError_t launch_expand_groups(const K1Plan* d_plans, uint32_t nplans, uint32_t ngroups, K1Group* d_groups,
                                 hipStream_t s);
 bool tail_gather_on();  // option k1_gather = 0: leftover chunks one per lane, no gathered waves
@@ -125,10 +135,11 @@ struct K1WaveTime {
     uint64_t real0, real1;    // s_memrealtime (100 MHz) before and after the body
     uint64_t clk0, clk1;      // s_memtime (shader clock) before and after the body
 };
-// partial: some groups have count < 64 (plan_block_sums_files) -- they run as gathered waves of the same launch
+// partial: some groups have count < 64 (plan_block_sums_files) -- they run as gathered waves of the same launch;
+// anyb: some groups are at B % 128 != 0 -- they run as any-B waves of the same launch
 hipError_t launch_block_sums_batch(const K1Group* d_groups, uint32_t ngroups, const K1Lane* d_lanes, uint32_t nlanes,
                                    int lane_align, uint32_t seed_word, hipStream_t s, const int* abort_flag = nullptr,
-                                   int abort_gen = 0, bool partial = false);
+                                   int abort_gen = 0, bool partial = false, bool anyb = false);
 
 // Chain flags for the Sender fast path: flag[k] = 1 iff source window k (aligned, from the source's
 // own block sums) has the same weak key and the same dl-byte digest as basis chunk k.

@@ -11,6 +11,7 @@
 
 #include "device.h"
 #include "device_common.h"
+#include "k1_plan.h"
 #include "md5_core.h"
 #include "options.h"
 
@@ -1098,6 +1099,263 @@ hipError_t launch_block_sums_segments(const K1Seg* d_segs, uint32_t nseg, const 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// K1 at any block length (option k1_anyb; 512 <= B <= 128 KiB, B % 128 != 0): shift_wave with one ring offset per
+// chunk instead of one per wave.  A wave owns 64 consecutive full-length chunks starting at any byte address.  Chunk c
+// starts a_c = (a_0 + c B) mod 128 bytes into a 128-B line; line u of a chunk is its bytes [128 u - a_c, +128).
+//  * Loads: every load is one whole aligned line per 8 lanes, as in the shift kernel: row j's lanes fetch line u of
+//    chunk 8 j + (l >> 3) at ((a_0 + c B) & ~127) + 128 u from the wave's first line (one 32-bit offset per row and
+//    lane).  Every chunk loads lines 0 .. nst + 1; the buffer descriptor ends with the line that holds the wave's last
+//    byte, so a line past it (chunk 63's line nst + 1 when its bytes end in line nst) reads as zero and touches nothing.
+//  * LDS: shift_wave's image, a two-line ring per chunk row (16 slots + 1 pad slot).  MD5 stage t of lane c is ring
+//    bytes [(128 t + a_c) mod 256, +128).  Of even stages that never wraps (a_c + 128 <= 255): the reads are the lane's
+//    base plus immediates.  Of odd stages each read's ring offset is taken mod 256.
+//  * K, the alignment class (k1_align_class: the widest of 16, 8, 4, 1 dividing the data's address and B), divides
+//    every a_c, and no LDS read is wider than it: ds_read_b128 (4 per block, no funnel), ds_read_b64, ds_read_b32,
+//    and for K = 1 the 17 dwords around the block funnel-shifted by a_c & 3 per lane (v_alignbyte_b32).
+//  * The remainder r = B & 127 is "stage nst": its 128 ring bytes are read like any stage's (line nst + 1 is loaded
+//    for it) and the bytes from r on are masked off -- r is wave-uniform, so the closing is uniform control flow.
+//    r >= 64: one more 64-B block.  Then t = r & 63 bytes, the seed, 0x80, zeros and the bit length: one block for
+//    t <= 51, two above (the seed straddles them for t = 61 .. 63).
+//  * Weak sums: the MFMA form over the 128 nst bytes (block_sums_pipe_body's weak_words); the r remainder bytes add
+//    to s1 and u on the VALU (weak_block over the masked words at offset 128 nst).  All mod 2^32.
+//  * Abort: polled once per two stages, as shift_wave.  PRE (batched groups): once before the first stage too.
+// ------------------------------------------------------------------------------------------------
+// bytes [pos, pos + 4) of a message whose first `lim` bytes are data: the mask of the data bytes
+__device__ __forceinline__ uint32_t anyb_mask(uint32_t lim, uint32_t pos) {
+    const uint32_t nb = lim > pos ? min(lim - pos, 4u) : 0u;
+    return nb >= 4u ? 0xFFFFFFFFu : (1u << (8u * nb)) - 1u;
+}
+// the word at byte 4 i of a stream that holds the 5 bytes seed, 0x80 from byte t on and zeros elsewhere
+__device__ __forceinline__ uint32_t anyb_pad(uint32_t seed, uint32_t t, int i) {
+    const uint64_t v = (uint64_t)seed | (0x80ull << 32);
+    const int d = 4 * i - (int)t;
+    if (d >= 8 || d <= -4) return 0u;
+    return d >= 0 ? (uint32_t)(v >> (8 * d)) : (uint32_t)(v << (8 * -d));
+}
+
+template <int K, bool PRE>
+__device__ __forceinline__ void anyb_wave(const uint8_t* __restrict__ chunk0, uint32_t B, uint32_t dl, uint32_t seed,
+                                          int32_t* __restrict__ weak_out, uint8_t* __restrict__ strong_out,
+                                          const int* abort_flag, int abort_gen) {
+    static_assert(K == 16 || K == 8 || K == 4 || K == 1, "alignment class");
+    constexpr int ROWB = 17 * 16;                  // bytes per chunk row
+    constexpr int PS = K == 1 ? 4 : K;             // bytes per LDS read
+    constexpr int NR = K == 1 ? 17 : 16;           // dwords read per block
+    extern __shared__ __attribute__((aligned(16))) uint4 lds_all[];  // 64 rows of 17 slots
+    const uint8_t* lds_b = reinterpret_cast<const uint8_t*>(lds_all);
+    const int l = threadIdx.x;
+    const uint32_t nst = B >> 7;  // host guarantees 4 <= nst <= 1024
+    const uint32_t a0 = (uint32_t)(reinterpret_cast<uintptr_t>(chunk0) & 127u);
+    const uint8_t* gdata = chunk0 - a0;
+    const uint32_t al = (a0 + (uint32_t)l * B) & 127u;  // the lane's own chunk
+    const uint32_t alf = K == 1 ? al & ~3u : al, sh = al & 3u;
+    const int wr0 = (l >> 3) * 17 + (l & 7);
+    const uint32_t rowb = (uint32_t)l * ROWB;
+
+    v4i32 wW[4];  // the A operand for block quarter w (block_sums_pipe_body)
+    v4i32 accW = {0, 0, 0, 0}, RW = {0, 0, 0, 0};
+    {
+        const int m = l & 15, q = l >> 4, type = m >> 2;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                uint32_t word = 0;
+                if (q == (m & 3) && type == 0) word = 0x01010101u;
+                else if (q == (m & 3) && type == 1)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) word |= (uint32_t)(16 * w + 4 * d + b) << (8 * b);
+                wW[w][d] = (int)word;
+            }
+    }
+    uint4 q[2][8];      // line u + 1 and u + 2 in flight while step u computes
+    uint32_t Wa[NR];    // block 0 of the next MD5 stage
+    uint32_t Wb[NR];    // block 1 of the current MD5 stage
+    // the wave's lines: from the line of its first byte to the line of its last (past that, loads return zero)
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(gdata), 0, (int)((a0 + 64u * B + 127u) & ~127u), 0x00020000);
+    uint32_t loff[8];  // row j: line 0 of chunk 8 j + (l >> 3), piece l & 7
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        loff[j] = ((a0 + (uint32_t)(8 * j + (l >> 3)) * B) & ~127u) + 16u * (uint32_t)(l & 7);
+    auto load = [&](uint4 (&dst)[8], uint32_t line) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, loff[j] + 128u * line, 0, 2);
+            dst[j] = make_uint4(t.x, t.y, t.z, t.w);
+        }
+    };
+    auto put = [&](const uint4 (&src)[8], int half) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) lds_all[wr0 + j * 8 * 17 + 8 * half] = src[j];
+    };
+    // the words that hold block h of the MD5 stage with parity P (ring offset 128 P + a_c + 64 h)
+    auto get_words = [&](uint32_t (&w)[NR], auto pc, int h) __attribute__((always_inline)) {
+        constexpr int P = decltype(pc)::value;
+#pragma unroll
+        for (int i = 0; i < (4 * NR + PS - 1) / PS; ++i) {
+            const uint32_t off = 128u * P + 64u * (uint32_t)h + (uint32_t)(PS * i);
+            const uint32_t at = P == 0 ? rowb + alf + off : rowb + ((alf + off) & 255u);
+            if constexpr (K == 16) {
+                const uint4 v = *reinterpret_cast<const uint4*>(lds_b + at);
+                w[4 * i] = v.x;
+                w[4 * i + 1] = v.y;
+                w[4 * i + 2] = v.z;
+                w[4 * i + 3] = v.w;
+            } else if constexpr (K == 8) {
+                const uint2 v = *reinterpret_cast<const uint2*>(lds_b + at);
+                w[2 * i] = v.x;
+                w[2 * i + 1] = v.y;
+            } else {
+                w[i] = *reinterpret_cast<const uint32_t*>(lds_b + at);
+            }
+        }
+    };
+    auto words = [&](const uint32_t (&w)[NR], uint32_t (&m)[16]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            if constexpr (K == 1) m[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], sh);
+            else m[i] = w[i];
+        }
+    };
+    Md5State st = md5_init();
+    auto md5_block = [&](const uint32_t (&w)[NR]) __attribute__((always_inline)) {
+        uint32_t m[16];
+        words(w, m);
+        md5_stream_block(st, m);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) RW[e] += accW[e];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const v4i32 b4 = {(int)m[4 * k], (int)m[4 * k + 1], (int)m[4 * k + 2], (int)m[4 * k + 3]};
+            accW = __builtin_amdgcn_mfma_i32_16x16x64_i8(wW[k], b4, accW, 0, 0, 0);
+        }
+    };
+    // Step u (shift_wave's): line u sits in half P = u & 1.  PREV: MD5 of stage u - 1; then line u + 1 is written
+    // (half P ^ 1) and stage u's block 0 read; REFILL: load line u + 3 into the slot line u + 1 leaves.
+    auto step = [&](auto pc, uint32_t u, bool prev, bool refill) __attribute__((always_inline)) {
+        constexpr int P = decltype(pc)::value;
+        if (prev) get_words(Wb, std::integral_constant<int, P ^ 1>{}, 1);  // before line u + 1 replaces line u - 1
+        compiler_fence();
+        put(q[P ^ 1], P ^ 1);
+        if (refill) load(q[P ^ 1], u + 3);
+        if (prev) md5_block(Wa);
+        compiler_fence();
+        get_words(Wa, pc, 0);  // lines u and u + 1
+        if (prev) md5_block(Wb);
+        compiler_fence();
+    };
+
+    load(q[0], 0);
+    load(q[1], 1);
+    if constexpr (PRE) {  // a group whose file was resolved before the wave started does nothing
+        if (poll_abort(abort_flag) == abort_gen) return;
+    }
+    put(q[0], 0);
+    load(q[0], 2);
+    compiler_fence();
+    step(std::integral_constant<int, 0>{}, 0, false, true);  // (line 3 <= nst + 1)
+    uint32_t u = 1;
+    int flag = 0;
+    // steady state: both steps refill (u + 4 <= nst + 1); the last step is nst, which writes line nst + 1
+    for (; u + 3 <= nst && flag != abort_gen; u += 2) {
+        asm volatile("s_load_dword %0, %1, 0x0 glc" : "=s"(flag) : "s"(abort_flag));
+        step(std::integral_constant<int, 1>{}, u, true, true);
+        step(std::integral_constant<int, 0>{}, u + 1, true, true);
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(flag));
+    }
+    if (flag == abort_gen) return;
+    for (; u <= nst; u += 2) {  // drain
+        step(std::integral_constant<int, 1>{}, u, true, u + 2 <= nst);
+        if (u + 1 <= nst) step(std::integral_constant<int, 0>{}, u + 1, true, u + 3 <= nst);
+    }
+    // "stage nst": Wa holds its block 0; its block 1 from lines nst and nst + 1
+    if (nst & 1) get_words(Wb, std::integral_constant<int, 1>{}, 1);
+    else get_words(Wb, std::integral_constant<int, 0>{}, 1);
+    const uint32_t r = B & 127u, t = r & 63u;
+    uint32_t m0[16], m1[16], tw[16];
+    words(Wa, m0);
+    words(Wb, m1);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        m0[i] &= anyb_mask(r, 4u * i);
+        m1[i] &= anyb_mask(r, 64u + 4u * i);
+    }
+    int32_t xs1 = 0, xu = 0;  // the remainder's weak sums
+    weak_block(m0, xs1, xu, 128u * nst);
+    weak_block(m1, xs1, xu, 128u * nst + 64u);
+    if (r >= 64u) md5_compress(st, m0);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tw[i] = r >= 64u ? m1[i] : m0[i];
+    const uint64_t bits = ((uint64_t)B + 4) * 8;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tw[i] |= anyb_pad(seed, t, i);
+    if (t <= 51u) {
+        tw[14] = (uint32_t)bits;
+        tw[15] = (uint32_t)(bits >> 32);
+        md5_compress(st, tw);
+    } else {
+        md5_compress(st, tw);
+        uint32_t m2[16];
+#pragma unroll
+        for (int i = 0; i < 14; ++i) m2[i] = anyb_pad(seed, t, 16 + i);
+        m2[14] = (uint32_t)bits;
+        m2[15] = (uint32_t)(bits >> 32);
+        md5_compress(st, m2);
+    }
+    // as block_sums_pipe_body: chunk n + 16 q's sums in lane n (element q) and lane n + 16
+#pragma unroll
+    for (int e = 0; e < 4; ++e) RW[e] += accW[e];
+    const int n = l & 15, qq = l >> 4;
+    int32_t tS[4], tR[4], tW[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        tS[e] = __shfl(accW[e], n, 64);
+        tR[e] = __shfl(RW[e], n, 64);
+        tW[e] = __shfl(accW[e], n + 16, 64);
+    }
+    const int32_t S = qq == 0 ? tS[0] : qq == 1 ? tS[1] : qq == 2 ? tS[2] : tS[3];
+    const int32_t Rq = qq == 0 ? tR[0] : qq == 1 ? tR[1] : qq == 2 ? tR[2] : tR[3];
+    const int32_t Wq = qq == 0 ? tW[0] : qq == 1 ? tW[1] : qq == 2 ? tW[2] : tW[3];
+    const int32_t s1 = S + xs1;
+    const int32_t uw = (int32_t)(64u * (2u * nst * (uint32_t)S - (uint32_t)Rq)) + Wq + xu;
+    const int32_t s2 = (int32_t)(B * (uint32_t)s1 - (uint32_t)uw);
+    weak_out[l] = (int32_t)(((uint32_t)s1 & 0xFFFFu) | ((uint32_t)s2 << 16));
+    store_digest(strong_out + (size_t)l * dl, st, dl);
+}
+
+// the class of a wave from its first chunk's address and B (both wave-uniform)
+template <bool PRE>
+__device__ __forceinline__ void anyb_wave_any(const uint8_t* __restrict__ chunk0, uint32_t B, uint32_t dl, uint32_t seed,
+                                              int32_t* __restrict__ weak_out, uint8_t* __restrict__ strong_out,
+                                              const int* abort_flag, int abort_gen) {
+    const uint32_t v = __builtin_amdgcn_readfirstlane((int)((uint32_t)reinterpret_cast<uintptr_t>(chunk0) | B));
+    if ((v & 15u) == 0) anyb_wave<16, PRE>(chunk0, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen);
+    else if ((v & 7u) == 0) anyb_wave<8, PRE>(chunk0, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen);
+    else if ((v & 3u) == 0) anyb_wave<4, PRE>(chunk0, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen);
+    else anyb_wave<1, PRE>(chunk0, B, dl, seed, weak_out, strong_out, abort_flag, abort_gen);
+}
+
+// The single-file launch: main waves [first_wave, first_wave + main_waves) of the file (k1_plan.h: the waves whose
+// lines lie in the readable bounds), then the lane waves in the same launch: one lane per chunk before and after
+// the main waves' chunks (plain dwordx4 loads at the lane's own address, as the pipelined kernel's tail waves).
+template <int K>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void block_sums_anyb_kernel(
+    const uint8_t* __restrict__ data, int64_t n, uint32_t B, uint32_t nchunks, uint32_t first_wave, uint32_t main_waves,
+    uint32_t dl, uint32_t seed, int32_t* __restrict__ weak_out, uint8_t* __restrict__ strong_out, const int* abort_flag,
+    int abort_gen) {
+    if (blockIdx.x >= main_waves) {
+        const uint32_t i = (blockIdx.x - main_waves) * 64u + threadIdx.x;
+        const uint32_t c = i < 64u * first_wave ? i : i + 64u * main_waves;
+        if (c < nchunks) lane_chunk_sums<16, 4, false>(data, n, B, c, dl, seed, weak_out, strong_out);
+        return;
+    }
+    const uint32_t c0 = (first_wave + blockIdx.x) * 64u;
+    anyb_wave<K, false>(data + (size_t)c0 * B, B, dl, seed, weak_out + c0, strong_out + (size_t)c0 * dl, abort_flag,
+                        abort_gen);
+}
+constexpr uint32_t kAnybLds = 64 * 17 * sizeof(uint4);
 
 constexpr uint32_t kCUs = 256;            // MI355X compute units
 
@@ -1125,9 +1383,14 @@ static void k1_launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, uint32_t 
     }
 }
 
-// The single-file K1.  variant -1: the production choice -- the pipelined K1 (with its gathered tail) or, at a base
-// off a 128-B line, the line-aligned shift kernel; the per-lane kernel for the shapes they do not take.  variant 0
-// (kbench's parity reference): the per-lane kernel for every chunk.
+// The single-file K1.  variant -1: the production choice (k1_plan_single, k1_plan.h) -- the pipelined K1 (with its
+// gathered tail), at a base off a 128-B line the line-aligned shift kernel, at B % 128 != 0 the any-B kernel; the
+// per-lane kernel for the shapes they do not take.  variant 0 (kbench's parity reference): the per-lane kernel for
+// every chunk.
+K1PlanOpts k1_plan_opts() {
+    return K1PlanOpts{opt(OPT_K1_ANYB) != 0, opt(OPT_K1_SHIFT) != 0, opt(OPT_K1_UNALIGNED) != 0, k1_dma_on(),
+                      tail_gather_on()};
+}
 #ifndef RSH_KBENCH
 static
 #endif
@@ -1158,6 +1421,11 @@ hipError_t launch_block_sums_variant(int variant, const uint8_t* d_data, int64_t
                                dl, seed_word, d_weak, d_strong, word, abort_flag ? abort_gen : -1, k1_prio(nchunks / 64));
         return hipGetLastError();
     }
+    if (variant == 1032) {  // every chunk per lane, plain dwordx4 loads at the lane's own address (any B, any base)
+        hipLaunchKernelGGL((block_sums_kernel<16, 4, false>), dim3((nchunks + 63) / 64), dim3(64), 0, s, d_data, n, B,
+                           nchunks, dl, seed_word, d_weak, d_strong, 0u);
+        return hipGetLastError();
+    }
     if (variant == 1010) {  // the VALU weak-sum form over whole waves (kbench shapes: n = 64 k B, 128-B aligned)
         if ((B % 128) != 0 || nst < 4 || nst > 1024 || n != (int64_t)nchunks * B || nchunks % 64 != 0 || (addr % 128) != 0)
             return hipErrorInvalidValue;
@@ -1167,86 +1435,80 @@ hipError_t launch_block_sums_variant(int variant, const uint8_t* d_data, int64_t
         return hipGetLastError();
     }
 #endif
-    // the pipelined and shift kernels poll an abort word (never_word() for launches without one of their own)
-    const bool coalesced = variant < 0 && abort_flag && (B % 128) == 0 && nst >= 4 && nst <= 1024;
-    // A base that is not 128-B aligned goes to the line-aligned shift kernel when the lines it reads around the
-    // data -- a bytes before it, up to 128 - a after the last full wave -- lie in the same allocation (option
-    // k1_shift = 0, test: the pipelined kernel at the unaligned base, its path when the lines do not fit).
-    if (coalesced && (addr % 128) != 0 && opt(OPT_K1_SHIFT) != 0) {
+    // the pipelined, shift and any-B kernels poll an abort word (never_word() for launches without one of their own)
+    const bool coalescable = variant < 0 && abort_flag;
+    // the data's allocation, for the forms that read whole lines around the data (shift, any-B)
+    uint64_t alloc_lo = 0, alloc_size = 0;
+    if (coalescable && nst >= 4 && nst <= 1024 && ((addr % 128) != 0 || (B % 128) != 0)) {
         hipDeviceptr_t lo = nullptr;
         size_t size = 0;
-        const uint32_t a = (uint32_t)(addr % 128);
         if (hipMemGetAddressRange(&lo, &size, reinterpret_cast<hipDeviceptr_t>(const_cast<uint8_t*>(d_data))) ==
-                hipSuccess &&
-            addr - a >= reinterpret_cast<uintptr_t>(lo)) {
-            const int64_t avail = (int64_t)(reinterpret_cast<uintptr_t>(lo) + size - (addr - a));
-            const uint32_t nfullc = (uint32_t)std::min<int64_t>(n / B, nchunks);
-            const int64_t fit = avail >= 128 ? (avail - 128) / ((int64_t)64 * B) : 0;
-            const uint32_t mw = (uint32_t)std::min<int64_t>(nfullc / 64, fit);
-            if (mw > 0) {
-                uint32_t tail_waves = (nchunks - 64 * mw + 63) / 64;
-                // full-length leftovers gathered into coalesced waves when that adds no wave or every wave fits
-                // the chip's slots (as block_sums_pipe_tailg_kernel); LDS then for the gathered body's buffers
-                const uint32_t tail_full = nfullc - 64 * mw, tail_short = nchunks - nfullc;
-                const uint32_t gwaves = (tail_full + 63) / 64 + (tail_short + 63) / 64;
-                const bool gather = tail_full > 0 && tail_gather_on() &&
-                                    (gwaves == tail_waves || mw + gwaves <= 2 * 4 * kCUs);
-                const uint32_t tf = gather ? tail_full : 0u;
-                if (gather) tail_waves = gwaves;
-                const dim3 grid(mw + tail_waves);
-                const size_t lb = gather ? 2 * 64 * 9 * sizeof(uint4) : 64 * 17 * sizeof(uint4);
-                switch ((a >> 2) & 3) {
-                    case 0:
-                        k1_launch(block_sums_shift_kernel<0>, grid, dim3(64), (uint32_t)lb, s, d_data, n, a, B, nchunks,
-                                  mw, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, tf);
-                        break;
-                    case 1:
-                        k1_launch(block_sums_shift_kernel<1>, grid, dim3(64), (uint32_t)lb, s, d_data, n, a, B, nchunks,
-                                  mw, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, tf);
-                        break;
-                    case 2:
-                        k1_launch(block_sums_shift_kernel<2>, grid, dim3(64), (uint32_t)lb, s, d_data, n, a, B, nchunks,
-                                  mw, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, tf);
-                        break;
-                    default:
-                        k1_launch(block_sums_shift_kernel<3>, grid, dim3(64), (uint32_t)lb, s, d_data, n, a, B, nchunks,
-                                  mw, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, tf);
-                }
-                return hipGetLastError();
-            }
+            hipSuccess) {
+            alloc_lo = reinterpret_cast<uintptr_t>(lo);
+            alloc_size = size;
         }
     }
-    // The pipelined K1 also runs at base addresses that are not 16-B aligned (the phase-shifted speculation
-    // starts at src + s for any s): its dwordx4 buffer loads then straddle 16-B boundaries, which gfx950
-    // serves in its unaligned access mode (bit-exact against the oracle at offsets 0..15,
-    // test_k1_unaligned_base).  Option k1_unaligned = 0 (test) sends such bases to the per-lane kernel instead.
-    const uint32_t waves = (uint32_t)std::min<int64_t>(n / B, nchunks) / 64;
-    if (coalesced && waves > 0 && ((addr % 16) == 0 || opt(OPT_K1_UNALIGNED) != 0)) {
-        const uint32_t nfullc = (uint32_t)std::min<int64_t>(n / B, nchunks);  // chunks with L == B
+    K1PlanOpts po = k1_plan_opts();
+    po.dma = dma_on;
+    const K1Single P = k1_plan_single(addr, alloc_lo, alloc_size, n, B, nchunks, coalescable, po);
+    if (P.form == K1_FORM_ANYB) {
+        const dim3 grid(P.main_waves + P.tail_waves);
+        auto go = [&](auto kernel) {
+            k1_launch(kernel, grid, dim3(64), kAnybLds, s, d_data, n, B, nchunks, P.first_wave, P.main_waves, dl,
+                      seed_word, d_weak, d_strong, abort_flag, abort_gen);
+        };
+        switch (P.align_class) {
+            case 16: go(block_sums_anyb_kernel<16>); break;
+            case 8: go(block_sums_anyb_kernel<8>); break;
+            case 4: go(block_sums_anyb_kernel<4>); break;
+            default: go(block_sums_anyb_kernel<1>);
+        }
+        return hipGetLastError();
+    }
+    if (P.form == K1_FORM_SHIFT) {
+        const uint32_t a = P.a, mw = P.main_waves, tf = P.gathered;
+        const dim3 grid(mw + P.tail_waves);
+        // LDS: the ring, or the gathered body's buffers
+        const size_t lb = tf > 0 ? 2 * 64 * 9 * sizeof(uint4) : 64 * 17 * sizeof(uint4);
+        switch ((a >> 2) & 3) {
+            case 0:
+                k1_launch(block_sums_shift_kernel<0>, grid, dim3(64), (uint32_t)lb, s, d_data, n, a, B, nchunks,
+                          mw, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, tf);
+                break;
+            case 1:
+                k1_launch(block_sums_shift_kernel<1>, grid, dim3(64), (uint32_t)lb, s, d_data, n, a, B, nchunks,
+                          mw, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, tf);
+                break;
+            case 2:
+                k1_launch(block_sums_shift_kernel<2>, grid, dim3(64), (uint32_t)lb, s, d_data, n, a, B, nchunks,
+                          mw, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, tf);
+                break;
+            default:
+                k1_launch(block_sums_shift_kernel<3>, grid, dim3(64), (uint32_t)lb, s, d_data, n, a, B, nchunks,
+                          mw, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, tf);
+        }
+        return hipGetLastError();
+    }
+    if (P.form == K1_FORM_PIPE_DMA || P.form == K1_FORM_PIPE_REG) {
+        const uint32_t waves = P.main_waves;
         const size_t wave_lds = 64 * 9 * sizeof(uint4);
         // the pipelined K1 at any wave count (occupancy pinned to 2 waves/SIMD; beyond 2048 waves they run in
         // rounds): measured 3.19 vs 3.96 ms for 16 GiB at B = 64 KiB (4096 waves) against the unpinned
         // instantiation, and ahead of the round-1 coalesced kernel at every size
-        const uint32_t tail_waves = (nchunks - 64 * waves + 63) / 64;  // in the same launch
-        // the partial last wave's full chunks gathered into a coalesced wave when that adds no wave or every wave
-        // still fits the chip's slots (2 per SIMD)
-        const uint32_t tail_full = nfullc - 64 * waves, tail_short = nchunks - nfullc;
-        const uint32_t gwaves = (tail_full + 63) / 64 + (tail_short + 63) / 64;
-        // the DMA form where every wave's base (d_data + 64 k B) is 16-B aligned: its loads write whole 16-B LDS slots
-        const bool dma = dma_on && (addr % 16) == 0;
+        const bool dma = P.form == K1_FORM_PIPE_DMA;
         const uint32_t prio = k1_prio(waves);
-        if (tail_full > 0 && tail_gather_on() && (gwaves == tail_waves || waves + gwaves <= 2 * 4 * kCUs)) {
+        if (P.gathered > 0) {
             // LDS: the gathered waves' two 9-slot buffers (above the DMA form's two 8 KiB slots)
-            k1_launch(dma ? block_sums_pipe_tailg_kernel : block_sums_pipe_tailg_reg_kernel, dim3(waves + gwaves),
-                      dim3(64), (uint32_t)(2 * wave_lds), s, d_data, B, dl, seed_word, d_weak, d_strong, abort_flag,
-                      abort_gen, n, nchunks, waves, tail_full, prio);
+            k1_launch(dma ? block_sums_pipe_tailg_kernel : block_sums_pipe_tailg_reg_kernel,
+                      dim3(waves + P.tail_waves), dim3(64), (uint32_t)(2 * wave_lds), s, d_data, B, dl, seed_word, d_weak,
+                      d_strong, abort_flag, abort_gen, n, nchunks, waves, P.gathered, prio);
             return hipGetLastError();
         }
         if (dma)
-            k1_launch(block_sums_pipe_kernel<false>, dim3(waves + tail_waves), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
+            k1_launch(block_sums_pipe_kernel<false>, dim3(waves + P.tail_waves), dim3(64), 2 * K1_DMA_STAGE, s, d_data, B,
                       dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves, prio);
         else
-            k1_launch(block_sums_pipe_reg_kernel<false>, dim3(waves + tail_waves), dim3(64), (uint32_t)(2 * wave_lds), s,
+            k1_launch(block_sums_pipe_reg_kernel<false>, dim3(waves + P.tail_waves), dim3(64), (uint32_t)(2 * wave_lds), s,
                       d_data, B, dl, seed_word, d_weak, d_strong, abort_flag, abort_gen, nullptr, n, nchunks, waves, prio);
         return hipGetLastError();
     }
@@ -1266,84 +1528,104 @@ hipError_t launch_block_sums_variant(int variant, const uint8_t* d_data, int64_t
     return hipGetLastError();
 }
 
+static K1FileCut cut_file(const K1File& F, const K1PlanOpts& po) {
+    return k1_plan_file(reinterpret_cast<uintptr_t>(F.data), reinterpret_cast<uintptr_t>(F.lo),
+                        reinterpret_cast<uintptr_t>(F.hi), F.n, F.B, F.nchunks, po);
+}
+// the lane waves of a file's chunks [0, c_lo) and [c_hi, nchunks) (what its groups do not cover)
+static void lane_waves(const K1File& F, int32_t f, uint32_t c_lo, uint32_t c_hi, std::vector<K1Lane>* lanes,
+                       int* lane_align) {
+    const uintptr_t addr = reinterpret_cast<uintptr_t>(F.data);
+    const int a = ((F.B % 16) == 0 && (addr % 16) == 0) ? 16 : ((F.B % 4) == 0 && (addr % 4) == 0) ? 4 : 1;
+    for (uint32_t c = 0; c < c_lo; c += 64) {  // (c_lo is 0 or 64: an any-B file's wave 0)
+        lanes->push_back(K1Lane{F.data, F.n, F.weak, F.strong, F.B, F.dl, c, std::min(c_lo, F.nchunks), f});
+        *lane_align = std::min(*lane_align, a);
+    }
+    for (uint32_t c = c_hi; c < F.nchunks; c += 64) {
+        lanes->push_back(K1Lane{F.data, F.n, F.weak, F.strong, F.B, F.dl, c, F.nchunks, f});
+        *lane_align = std::min(*lane_align, a);
+    }
+}
+
 void plan_block_sums_batch(const K1File* files, int32_t nfiles, std::vector<K1Group>* groups,
-                           std::vector<K1Lane>* lanes, int* lane_align) {
+                           std::vector<K1Lane>* lanes, int* lane_align, bool* anyb) {
     groups->clear();
     lanes->clear();
     *lane_align = 16;
+    if (anyb) *anyb = false;
+    const K1PlanOpts po = k1_plan_opts();
     for (int32_t f = 0; f < nfiles; ++f) {
         const K1File& F = files[f];
         if (F.nchunks == 0 || F.B == 0) continue;
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(F.data);
-        const uint32_t nst = F.B >> 7;
-        uint32_t c = 0;
-        if ((F.B % 128) == 0 && nst >= 4 && nst <= 1024 && (addr % 16) == 0) {  // the pipelined K1's shape
-            const uint32_t nfullc = (uint32_t)std::min<int64_t>(F.n / F.B, F.nchunks);
-            for (; c + 64 <= nfullc; c += 64)
-                groups->push_back(
-                    K1Group{F.data + (size_t)c * F.B, F.weak + c, F.strong + (size_t)c * F.dl, F.B, F.dl, nullptr, f});
-        }
-        for (; c < F.nchunks; c += 64) {
-            lanes->push_back(K1Lane{F.data, F.n, F.weak, F.strong, F.B, F.dl, c, F.nchunks, f});
-            const int a = ((F.B % 16) == 0 && (addr % 16) == 0) ? 16 : ((F.B % 4) == 0 && (addr % 4) == 0) ? 4 : 1;
-            *lane_align = std::min(*lane_align, a);
-        }
+        const K1FileCut cut = cut_file(F, po);  // the pipelined K1's shape, or the any-B wave's
+        const uint32_t c0 = 64 * cut.first_wave, c1 = c0 + 64 * cut.waves;
+        for (uint32_t c = c0; c < c1; c += 64)
+            groups->push_back(
+                K1Group{F.data + (size_t)c * F.B, F.weak + c, F.strong + (size_t)c * F.dl, F.B, F.dl, nullptr, f});
+        if (anyb && cut.form == K1_FORM_ANYB) *anyb = true;
+        lane_waves(F, f, cut.waves ? c0 : 0, cut.waves ? c1 : 0, lanes, lane_align);
     }
 }
 
 
 uint32_t plan_block_sums_files(const K1File* files, int32_t nfiles, std::vector<K1Plan>* plans,
-                               std::vector<K1Lane>* lanes, int* lane_align, bool* partial) {
+                               std::vector<K1Lane>* lanes, int* lane_align, bool* partial, bool* anyb) {
     plans->clear();
     lanes->clear();
     *lane_align = 16;
+    if (anyb) *anyb = false;
+    const K1PlanOpts po = k1_plan_opts();
     bool want_partial = partial && *partial;
     if (partial) *partial = false;
     if (want_partial) {
         // partial groups + one lane per short chunk, or (as without them) one lane wave per file tail: whichever
         // needs fewer rounds of the chip's wave slots (a wave past the last full round waits for a free slot;
-        // the lanes run in the same launch, launch_block_sums_batch)
-        uint64_t full = 0, w_part = 0, shorts = 0, w_lane = 0;
+        // the lanes run in the same launch, launch_block_sums_batch).  Any-B files have no partial groups: their
+        // leftovers are lane waves either way.
+        uint64_t full = 0, w_part = 0, shorts = 0, w_lane = 0, w_anyb = 0;
         for (int32_t f = 0; f < nfiles; ++f) {
             const K1File& F = files[f];
             if (F.nchunks == 0 || F.B == 0) continue;
-            const uint32_t nst = F.B >> 7;
-            const uintptr_t addr = reinterpret_cast<uintptr_t>(F.data);
-            uint32_t nfullc = 0;
-            if ((F.B % 128) == 0 && nst >= 4 && nst <= 1024 && (addr % 16) == 0)
-                nfullc = (uint32_t)std::min<int64_t>(F.n / F.B, F.nchunks);
+            const K1FileCut cut = cut_file(F, po);
+            if (cut.form == K1_FORM_ANYB) {
+                full += cut.waves;
+                w_anyb += cut.first_wave + (F.nchunks - 64 * (cut.first_wave + cut.waves) + 63) / 64;
+                continue;
+            }
+            const uint32_t nfullc = cut.nfullc;
             full += nfullc / 64;
             w_part += (nfullc % 64) ? 1 : 0;
             shorts += F.nchunks - nfullc;
             w_lane += (F.nchunks - 64 * (nfullc / 64) + 63) / 64;
         }
         const uint64_t slots = 2ull * 4 * kCUs;
-        const uint64_t r_part = (full + w_part + (shorts + 63) / 64 + slots - 1) / slots;
-        const uint64_t r_lane = (full + w_lane + slots - 1) / slots;
+        const uint64_t r_part = (full + w_anyb + w_part + (shorts + 63) / 64 + slots - 1) / slots;
+        const uint64_t r_lane = (full + w_anyb + w_lane + slots - 1) / slots;
         want_partial = w_part > 0 && r_part <= r_lane;
     }
     uint32_t g = 0;
     for (int32_t f = 0; f < nfiles; ++f) {  // the same cut as plan_block_sums_batch
         const K1File& F = files[f];
         if (F.nchunks == 0 || F.B == 0) continue;
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(F.data);
-        const uint32_t nst = F.B >> 7;
-        uint32_t c = 0;
-        if ((F.B % 128) == 0 && nst >= 4 && nst <= 1024 && (addr % 16) == 0) {
-            const uint32_t nfullc = (uint32_t)std::min<int64_t>(F.n / F.B, F.nchunks);
+        const K1FileCut cut = cut_file(F, po);
+        uint32_t c_lo = 0, c_hi = 0;
+        if (cut.form == K1_FORM_ANYB) {
+            c_lo = 64 * cut.first_wave;
+            c_hi = c_lo + 64 * cut.waves;
+            plans->push_back(K1Plan{F.data, F.weak, F.strong, F.B, F.dl, g, cut.waves, nullptr, f, 64 * cut.waves, c_lo});
+            g += cut.waves;
+            if (anyb) *anyb = true;
+        } else if (cut.form != K1_FORM_LANE) {
+            const uint32_t nfullc = cut.nfullc;
             // the full chunks past the last full wave: a partial group (gathered wave) or lanes
             const uint32_t ng = want_partial ? (nfullc + 63) / 64 : nfullc / 64;
             const uint32_t cov = std::min(nfullc, 64 * ng);
             if (ng > 0) plans->push_back(K1Plan{F.data, F.weak, F.strong, F.B, F.dl, g, ng, nullptr, f, cov});
             if (cov % 64 != 0) *partial = true;
             g += ng;
-            c = cov;
+            c_hi = cov;
         }
-        for (; c < F.nchunks; c += 64) {
-            lanes->push_back(K1Lane{F.data, F.n, F.weak, F.strong, F.B, F.dl, c, F.nchunks, f});
-            const int a = ((F.B % 16) == 0 && (addr % 16) == 0) ? 16 : ((F.B % 4) == 0 && (addr % 4) == 0) ? 4 : 1;
-            *lane_align = std::min(*lane_align, a);
-        }
+        lane_waves(F, f, c_lo, c_hi, lanes, lane_align);
     }
     return g;
 }
@@ -1359,9 +1641,9 @@ __global__ __launch_bounds__(256) void expand_groups_kernel(const K1Plan* __rest
         else hi = mid;
     }
     const K1Plan& P = plans[lo];
-    const uint32_t c = 64 * (t - P.g0);
+    const uint32_t k = 64 * (t - P.g0), c = P.c0 + k;
     groups[t] = K1Group{P.data + (size_t)c * P.B, P.weak + c, P.strong + (size_t)c * P.dl, P.B, P.dl, P.abort, P.file,
-                        min(64u, P.nfull - c)};
+                        min(64u, P.nfull - k)};
 }
 
 hipError_t launch_expand_groups(const K1Plan* d_plans, uint32_t nplans, uint32_t ngroups, K1Group* d_groups,
@@ -1418,15 +1700,61 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void bloc
     block_sums_pipe_body<true, false, false, DMA>(nullptr, 0u, 0u, seed, nullptr, nullptr, abort_flag, abort_gen, groups);
 }
 
+// The batched K1 of a launch with groups at B % 128 != 0: block_sums_pipe_multi_g_kernel with the any-B wave for
+// those groups (its class from the group's address and B; K1Group::abort honoured, and polled once before the first
+// stage).  The lane waves' load form is a launch argument here instead of a template parameter.
+template <bool DMA>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(256))) void block_sums_anyb_multi_kernel(
+    const K1Group* __restrict__ groups, uint32_t ngroups, const K1Lane* __restrict__ lanes, int lane_align,
+    uint32_t seed, const int* abort_flag, int abort_gen) {
+    if (blockIdx.x >= ngroups) {
+        const K1Lane e = lanes[blockIdx.x - ngroups];
+        const uint32_t c = e.c_first + threadIdx.x;
+        if (c >= e.nchunks) return;
+        if (lane_align == 16) lane_chunk_sums<16, 4, true>(e.data, e.n, e.B, c, e.dl, seed, e.weak, e.strong);
+        else if (lane_align == 4) lane_chunk_sums<4, 2, true>(e.data, e.n, e.B, c, e.dl, seed, e.weak, e.strong);
+        else lane_chunk_sums<0, 4, false>(e.data, e.n, e.B, c, e.dl, seed, e.weak, e.strong);
+        return;
+    }
+    const K1Group g = groups[blockIdx.x];
+    if (g.B & 127u) {
+        anyb_wave_any<true>(g.data, g.B, g.dl, seed, g.weak, g.strong, g.abort ? g.abort : abort_flag, abort_gen);
+        return;
+    }
+    if (g.count < 64) {
+        block_sums_pipe_body<false, true>(g.data, g.B, g.dl, seed, g.weak, g.strong,
+                                                           g.abort ? g.abort : abort_flag, abort_gen, nullptr, 0, 0,
+                                                           0xFFFFFFFFu, nullptr, g.count);
+        return;
+    }
+    block_sums_pipe_body<true, false, false, DMA>(nullptr, 0u, 0u, seed, nullptr, nullptr, abort_flag, abort_gen, groups);
+}
+
 hipError_t launch_block_sums_batch(const K1Group* d_groups, uint32_t ngroups, const K1Lane* d_lanes, uint32_t nlanes,
                                    int lane_align, uint32_t seed_word, hipStream_t s, const int* abort_flag,
-                                   int abort_gen, bool partial) {
-    const size_t lb = 2 * 64 * 9 * sizeof(uint4);  // a gathered wave's buffers (the DMA form's slots are 2 x 8 KiB)
+                                   int abort_gen, bool partial, bool anyb) {
+    // a gathered wave's buffers (the DMA form's slots are 2 x 8 KiB, the any-B ring 17 KiB)
+    const size_t lb = 2 * 64 * 9 * sizeof(uint4);
+    static_assert(kAnybLds <= 2 * 64 * 9 * sizeof(uint4) && 2 * K1_DMA_STAGE <= 2 * 64 * 9 * sizeof(uint4), "batched K1's LDS");
     // the planners cut groups only at 16-B aligned bases (plan_block_sums_batch / _files), so every group may take
     // the DMA form; files at other bases are lanes
     const bool dma = k1_dma_on();
     if (!abort_flag && (abort_flag = never_word()) != nullptr) abort_gen = -1;  // see never_word
     if (!abort_flag) return hipErrorOutOfMemory;  // never_word() failed: no uncached word for the pinned K1
+    if (anyb && ngroups > 0) {
+        // groups at B % 128 != 0 beside any others and the lanes: one launch (option k1_gather = 0 and no partial
+        // group: the lanes as a second launch, below)
+        const bool with_lanes = nlanes > 0 && (partial || tail_gather_on());
+        const dim3 grid(ngroups + (with_lanes ? nlanes : 0u));
+        if (dma)
+            hipLaunchKernelGGL((block_sums_anyb_multi_kernel<true>), grid, dim3(64), lb, s, d_groups, ngroups, d_lanes,
+                               lane_align, seed_word, abort_flag, abort_gen);
+        else
+            hipLaunchKernelGGL((block_sums_anyb_multi_kernel<false>), grid, dim3(64), lb, s, d_groups, ngroups, d_lanes,
+                               lane_align, seed_word, abort_flag, abort_gen);
+        if (with_lanes || nlanes == 0) return hipGetLastError();
+        ngroups = 0;  // the groups are launched
+    }
     // partial groups, or lanes beside groups: one launch (option k1_gather = 0: the lanes as a second launch)
     if (partial || (tail_gather_on() && nlanes > 0 && ngroups > 0)) {
         const dim3 grid(ngroups + nlanes);

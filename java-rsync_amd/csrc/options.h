@@ -51,6 +51,7 @@ enum Opt : int {
     OPT_SCAN_PHASE_MAP,    // single-file scan: phase launches after which the next hint that nothing covers maps the rest of
                            // the source (phase_map.h; 2 is the measured setting); 0, the default: never -- the map is a
                            // bet on a scan that lives, and one that a poisoned digest ends early loses it
+    OPT_K1_ANYB,           // 1: block lengths off a multiple of 128 (512 and up) take the coalesced any-B K1; 0: per lane
     OPT_COUNT
 };
 
@@ -69,7 +70,7 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"fault_inject", 0},        {"tokens_span", 256LL << 10}, {"tokens_piece", 8LL << 20},
     {"sums_piece", 32LL << 20}, {"tokens_runs", 64LL << 10}, {"k1_dma", 1},
     {"k1_prio", 1},             {"tokens_runs_batch", 4096}, {"resident_md5_bytes", 1LL << 30},
-    {"scan_phase_map", 0},
+    {"scan_phase_map", 0},      {"k1_anyb", 1},
 };
 
 inline const OptInfo* opt_info() { return kOpts; }

@@ -154,6 +154,15 @@ class TokenJob(ctypes.Structure):
                 ("out_len", ctypes.c_int64), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class K1PlanRec(ctypes.Structure):
+    """rsh_k1_plan: the K1 form a chunk set takes (rsh_debug_k1_plan, rsh_debug_k1_plan_batch)."""
+    _fields_ = [("form", ctypes.c_int32), ("align_class", ctypes.c_int32), ("main_waves", ctypes.c_uint32),
+                ("gathered_chunks", ctypes.c_uint32), ("lane_chunks", ctypes.c_uint32)]
+
+    def as_tuple(self):
+        return self.form, self.align_class, self.main_waves, self.gathered_chunks, self.lane_chunks
+
+
 class TokenFrameJob(ctypes.Structure):
     """rsh_token_frame_job: one file of rsh_tokens_frame_batch_device (device source and output, host events)."""
     _fields_ = [("d_src", ctypes.c_void_p), ("n", ctypes.c_int64), ("ev", ctypes.c_void_p), ("n_ev", ctypes.c_int64),
@@ -212,7 +221,8 @@ DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_rese
                  "rsh_debug_tokens_selftest", "rsh_debug_sums_selftest", "rsh_debug_tokens_scan_selftest",
                  "rsh_debug_untokens_selftest", "rsh_debug_k1_dma_swizzle", "rsh_debug_k1_wave_times",
                  "rsh_debug_tokens_scan_batch_selftest", "rsh_debug_phase_plan", "rsh_debug_phase_map_selftest",
-                 "rsh_debug_phase_round_b", "rsh_debug_phase_segments"]
+                 "rsh_debug_phase_round_b", "rsh_debug_phase_segments", "rsh_debug_k1_plan",
+                 "rsh_debug_k1_plan_batch"]
 
 _LIB = None
 
@@ -310,6 +320,9 @@ def lib():
         "rsh_debug_get_option": ([ctypes.c_char_p, ctypes.POINTER(I64)], ctypes.c_int),
         "rsh_debug_reset_options": ([], None),
         "rsh_debug_k1_dma_swizzle": ([I32, I32, I32], ctypes.c_int32),
+        "rsh_debug_k1_plan": ([ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, I64, I32, ctypes.POINTER(K1PlanRec)],
+                              ctypes.c_int),
+        "rsh_debug_k1_plan_batch": ([P, P, P, P, P, I32, ctypes.POINTER(K1PlanRec)], ctypes.c_int),
         "rsh_debug_k1_clock": ([P, P, I64, I32, I32, ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
         "rsh_debug_k1_wave_times": ([P, P, I64, I32, I32, P, I64, P, P], ctypes.c_int),
         "rsh_debug_streams_busy": ([P, ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
@@ -623,6 +636,25 @@ def phase_segments(samples, anchors, lo, n, block_length, chunk_count, min_windo
     _check(lib().rsh_debug_phase_segments(_ptr(a), _ptr(an), a.size, lo, n, block_length, chunk_count, min_windows,
                                           _ptr(segs), segs.size, ctypes.byref(k)))
     return [(int(g["s0"]), int(g["count"]), int(g["pref0"])) for g in segs[:k.value]]
+
+
+def k1_plan(addr, alloc_lo, alloc_size, n, block_length):
+    """rsh_debug_k1_plan: (form, align_class, main_waves, gathered_chunks, lane_chunks) of the single-file K1 launch over
+    n bytes at address addr inside the allocation [alloc_lo, alloc_lo + alloc_size) (size 0: unknown).  No device."""
+    r = K1PlanRec()
+    _check(lib().rsh_debug_k1_plan(addr, alloc_lo, alloc_size, n, block_length, ctypes.byref(r)))
+    return r.as_tuple()
+
+
+def k1_plan_batch(files):
+    """rsh_debug_k1_plan_batch over files = [(addr, lo, hi, n, block_length)] (lo == hi: the file's own bytes): one
+    (form, align_class, main_waves, gathered_chunks, lane_chunks) per file.  No device."""
+    nf = len(files)
+    cols = [np.array([f[i] for f in files], dt) for i, dt in
+            enumerate((np.uint64, np.uint64, np.uint64, np.int64, np.int32))]
+    out = (K1PlanRec * max(nf, 1))()
+    _check(lib().rsh_debug_k1_plan_batch(*[_ptr(c) for c in cols], nf, out))
+    return [out[i].as_tuple() for i in range(nf)]
 
 
 def set_option(name, value):

@@ -10,6 +10,9 @@
 // variant 1010: the pipelined K1 with its weak sums on the VALU (v_dot4) instead of the MFMAs (energy A/B).
 // variant 1020 / 1021: the production abortable launch in the DMA form / the register-staged form (option k1_dma);
 // variant 1022: the two interleaved launch by launch in one process.
+// variant 1032: every chunk on one lane with plain dwordx4 loads at the lane's own address, at any B and base (the
+// cheap alternative to the any-B form; variant 0 at B % 128 != 0 is today's per-lane choice: non-temporal loads).
+// KBENCH_ANYB=0: option k1_anyb off (1000, 1001, 1002 and 1005 then take the per-lane paths at B % 128 != 0).
 // variant 1100 + k (k = 0..63): the production abortable launch with option k1_prio = k (k >= 32: launches of more
 // than one round too); 1200 + k: k1_prio 0 and k interleaved launch by launch (0 runs the same instructions and sets
 // priority 0 every time, so the pair differs in the priorities alone, not in code placement).
@@ -479,6 +482,7 @@ int main(int argc, char** argv) {
         return 2;
     }
     // KBENCH_TRIM=t: t bytes fewer than the MiB count (a short last chunk, a partial last wave)
+    if (getenv("KBENCH_ANYB")) rsh::opt_table()[rsh::OPT_K1_ANYB].store(atoi(getenv("KBENCH_ANYB")));
     const int64_t n = ((int64_t)atoll(argv[1]) << 20) - (getenv("KBENCH_TRIM") ? atoll(getenv("KBENCH_TRIM")) : 0);
     const uint32_t B = (uint32_t)atoi(argv[2]), dl = (uint32_t)atoi(argv[3]);
     const int reps = atoi(argv[4]);
@@ -518,12 +522,13 @@ int main(int argc, char** argv) {
     const int64_t per = n / nfiles;
     for (int f = 0; f < nfiles; ++f) {
         const uint32_t cf = (uint32_t)((per + B - 1) / B), c0 = (uint32_t)((int64_t)f * per / B);
-        kf.push_back(rsh::K1File{d + (int64_t)f * per, per, B, dl, cf, w + c0, sx + (size_t)c0 * dl});
+        kf.push_back(rsh::K1File{d + (int64_t)f * per, per, B, dl, cf, w + c0, sx + (size_t)c0 * dl, d, d + n});
     }
     std::vector<rsh::K1Group> groups;
     std::vector<rsh::K1Lane> lanes;
     int lane_align = 16;
-    rsh::plan_block_sums_batch(kf.data(), nfiles, &groups, &lanes, &lane_align);
+    bool batch_anyb = false;
+    rsh::plan_block_sums_batch(kf.data(), nfiles, &groups, &lanes, &lane_align, &batch_anyb);
     rsh::K1Group* d_groups;
     rsh::K1Lane* d_lanes;
     CK(hipMalloc(&d_groups, (groups.size() + 1) * sizeof(rsh::K1Group)));
@@ -540,14 +545,14 @@ int main(int argc, char** argv) {
         const int64_t len = per - rag;
         const uint32_t c0 = (uint32_t)((int64_t)f * per / B);
         kr.push_back(rsh::K1File{d + (int64_t)f * per, len, B, dl, (uint32_t)((len + B - 1) / B), w + c0,
-                                 sx + (size_t)c0 * dl});
+                                 sx + (size_t)c0 * dl, d, d + n});
     }
     auto launch_rag = [&]() -> hipError_t {
         std::vector<rsh::K1Plan> plans;
         std::vector<rsh::K1Lane> rl;
         int ra = 16;
-        bool partial = rsh::tail_gather_on();
-        const uint32_t ng = rsh::plan_block_sums_files(kr.data(), nfiles, &plans, &rl, &ra, &partial);
+        bool partial = rsh::tail_gather_on(), anyb = false;
+        const uint32_t ng = rsh::plan_block_sums_files(kr.data(), nfiles, &plans, &rl, &ra, &partial, &anyb);
         static rsh::K1Plan* d_plans = nullptr;
         static rsh::K1Group* d_rg = nullptr;
         static rsh::K1Lane* d_rl = nullptr;
@@ -562,7 +567,7 @@ int main(int argc, char** argv) {
             printf("variant 1005: %u groups (partial %d), %zu lane waves\n", ng, (int)partial, rl.size());
         }
         return rsh::launch_block_sums_batch(d_rg, ng, d_rl, (uint32_t)rl.size(), ra, 0x04030201u, s, nullptr, 0,
-                                            partial);
+                                            partial, anyb);
     };
     // variant 1003: the segmented launch (block_sums_seg_kernel) over the whole buffer as one segment; the
     // buffer's base must be such that base - base % 128 is inside the allocation (KBENCH_OFFSET < 128)
@@ -597,7 +602,7 @@ int main(int argc, char** argv) {
         if (v == 1005) return launch_rag();
         if (v == 1002)
             return rsh::launch_block_sums_batch(d_groups, (uint32_t)groups.size(), d_lanes, (uint32_t)lanes.size(),
-                                                lane_align, 0x04030201u, s);
+                                                lane_align, 0x04030201u, s, nullptr, 0, false, batch_anyb);
         if (v == 1000) return rsh::launch_block_sums_variant(-1, d, n, B, C, dl, 0x04030201u, w, sx, s, abort_word, 1);
         if (v == 1010 || (v >= 1020 && v <= 1025 && v != 1022))
             return rsh::launch_block_sums_variant(v, d, n, B, C, dl, 0x04030201u, w, sx, s, abort_word, 1);
