@@ -422,6 +422,28 @@ typedef struct {
 } rsh_md5_job;
 int rsh_file_md5_batch(rsh_md5_job* jobs, int32_t njobs, int32_t threads);
 
+/* ---- whole-file MD5s of files in HBM (Sender.java:1241,1326; Receiver.java:824-842) ----
+ * What the *_device entry points leave to the caller, for files that stay in HBM: md5[16] of each job = MD5 of the n
+ * device bytes at d_data.  It is for MANY files: one file's MD5 is a serial chain, so each file runs on one lane of
+ * file_md5_kernel (64 files to a wave, longest first; DESIGN.md section 4, "Whole-file MD5s on the device") at about a
+ * tenth of a host core's rate (75 MB/s per file), and a segment's files run side by side.  A single file, or a few, are
+ * digested faster by downloading the bytes for rsh_file_md5_batch.  Measured on one MI355X against the download and
+ * the host's 16 cores: at files of 64 KiB this call wins from 64 files on, the fewest measured
+ * (0.90 against 1.13 ms), at files of 1 MiB from about 330 files on (14.0 ms whatever the count up to 8192, against
+ * 6.3 ms at 128 files and 38.5 ms at 1024).  A launch advances a file by at most option md5_device_slice bytes; longer
+ * files take several launches.
+ * Synchronous.  Per job: RSH_E_INVAL for n < 0, or n > 0 with a null d_data; the other files are still digested.
+ * Returns RSH_OK or the first failing job's status in file order (RSH_E_INVAL for a null ctx, or null jobs with
+ * njobs > 0).  njobs == 0 and a segment of empty files launch nothing; an empty file's digest is d41d8cd9...427e. */
+typedef struct {
+    const void* d_data;   /* device; any byte alignment */
+    int64_t n;
+    uint8_t md5[16];      /* out */
+    int32_t status;       /* out */
+    int32_t reserved;
+} rsh_md5_device_job;     /* 40 bytes */
+int rsh_file_md5_batch_device(rsh_ctx* ctx, rsh_md5_device_job* jobs, int32_t njobs);
+
 /* ---- Receiver (Receiver.java:459-555 combineDataToFile, :557-578 copies, :204-209 blockSize) ----
  * Replays one file's de-multiplexed token stream -- putInt(len)+bytes, putInt(-(i+1)), putInt(0), exactly
  * what rsh_tokens_write produces -- against the replica (the basis the Generator summed; NULL when the

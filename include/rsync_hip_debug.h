@@ -8,7 +8,12 @@
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
  * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio, tokens_runs_batch, resident_md5_bytes,
- * scan_phase_map, k1_anyb.
+ * scan_phase_map, k1_anyb, md5_device_slice, resident_md5, md5_lane_kbps, md5_link_kbps.
+ *
+ * resident_md5 = 0 (default): the segment Receiver's verify digests come down to the host; 1: file_md5_kernel digests
+ * every finished file where it lies, on the context's second stream; 2: the files up to the planner's length cut on the
+ * device and the longer ones on the host, side by side (md5_lane_kbps, md5_link_kbps: the planner's two rates in 1000
+ * bytes per second).  Results are identical in all three.  md5_device_slice: bytes per file and launch of the kernel.
  *
  * k1_anyb = 1 (default): block lengths of 512 and more that are no multiple of 128 take the coalesced any-B K1 (whole
  * 128-byte lines, one ring offset per chunk, abortable, timed), in single-file and batched launches; 0: every chunk of
@@ -47,7 +52,8 @@ void rsh_debug_reset_options(void);
 /* The duration of a K1 from its own dispatch timestamps (HIP events recorded by the launch, hipExtLaunchKernelGGL):
  * which 0 = the last rsh_block_sums_device's K1 (the Generator), 1 = the last single-file scan's aligned speculation
  * when it ran to completion, 2 = the last sums_frame_kernel / sums_unframe_kernel launch (HIP events around it),
- * 3 = the phase_map_kernel launch of the last rsh_debug_phase_map_selftest with a context (HIP events around it).
+ * 3 = the phase_map_kernel launch of the last rsh_debug_phase_map_selftest with a context (HIP events around it),
+ * 4 = the last file_md5_kernel launch (its own dispatch timestamps; option time_gen).
  * *ms = -1 when that launch was not timed: for which = 0, a shape with no coalesced wave (block lengths below 512, files
  * of fewer than 64 full chunks, k1_anyb = 0 at a block length off a multiple of 128) -- the per-lane kernel takes no
  * events. */
@@ -208,6 +214,35 @@ int rsh_debug_phase_round_b(const int64_t* samples, const rsh_phase_anchor* anch
 int rsh_debug_phase_segments(const int64_t* samples, const rsh_phase_anchor* anchors, int64_t count, int64_t lo,
                              int64_t n, int32_t block_length, int32_t chunk_count, int64_t min_windows,
                              rsh_phase_seg* segs, int64_t cap, int64_t* n_segs);
+
+/* Whole-file MD5s one lane per file (md5_file.h; rsh_file_md5_batch_device).  ctx == NULL: `data` is host memory and
+ * the host stand-in runs the kernel's grouping, slices and closing lane by lane; otherwise device memory and
+ * file_md5_kernel.  Per job the chain starts from `state` after `done` bytes (a multiple of 128 in 0 .. n; a fresh file
+ * is MD5's initial words and 0).  slice: bytes a launch advances a file by at most (a positive multiple of 128; 0:
+ * option md5_device_slice).  stop_after >= 0: at most that many launches; -1: until every file is closed.  On return
+ * closed = 1 and md5 holds the digest, or closed = 0 and state / done hold the chain where it stopped.  *launches: the
+ * launches made.  rsh_debug_kernel_ms(ctx, 4, ..) then gives the last launch's duration (option time_gen). */
+typedef struct {
+    const void* data;
+    int64_t n;
+    uint32_t state[4];  /* in / out */
+    int64_t done;       /* in / out */
+    uint8_t md5[16];    /* out */
+    int32_t closed;     /* out */
+    int32_t reserved;
+} rsh_md5_selftest_job; /* 64 bytes */
+int rsh_debug_md5_device_selftest(rsh_ctx* ctx, rsh_md5_selftest_job* jobs, int32_t njobs, int64_t slice,
+                                  int32_t stop_after, int32_t* launches);
+/* The closing blocks for the r < 128 bytes at `tail` that end a file of n bytes: blocks[0, 64 * *nblk), *nblk 1 .. 3. */
+int rsh_debug_md5_closing(const uint8_t* tail, int32_t r, int64_t n, uint8_t* blocks, int32_t* nblk);
+/* The next launch's grouping and the planner's cut, without a device.  n[i], done[i] (NULL: all 0): the files.  order
+ * (nfiles entries): the files that take a lane, wave w being order[64 w, 64 w + 64); *n_order their count; wave_nst
+ * (one entry per 64 files): each wave's stage count at `slice` (0: the option).  *cut: files of at most that length go
+ * to the kernel under resident_md5 = 2 at the given rates (1000 bytes per second; 0: the options md5_lane_kbps and
+ * md5_link_kbps), -1 when none does; *t_dev, *t_host: the plan's two times in seconds.  Any output may be NULL. */
+int rsh_debug_md5_plan(const int64_t* n, const int64_t* done, int32_t nfiles, int64_t slice, int64_t lane_kbps,
+                       int64_t link_kbps, int32_t* order, int32_t* n_order, uint32_t* wave_nst, int64_t* cut,
+                       double* t_dev, double* t_host);
 
 #ifdef __cplusplus
 }

@@ -206,10 +206,12 @@ int rsh_ctx_trim(rsh_ctx* ctx) {
     RSH_HIP(hipSetDevice(ctx->device));
     for (hipStream_t st : {ctx->stream, ctx->aux, ctx->phase}) RSH_HIP(hipStreamSynchronize(st));
     for (DevBuf* b : {&ctx->data, &ctx->weak, &ctx->strong, &ctx->seg_data, &ctx->seg_tab, &ctx->rcv[0], &ctx->rcv[1],
-                      &ctx->rcv_ops[0], &ctx->rcv_ops[1], &ctx->out, &ctx->sums_raw, &ctx->tokb_runs, &ctx->tokb_outs})
+                      &ctx->rcv_ops[0], &ctx->rcv_ops[1], &ctx->out, &ctx->sums_raw, &ctx->tokb_runs, &ctx->tokb_outs,
+                      &ctx->md5_lanes, &ctx->md5_out})
         b->release();
     for (PinnedBuf* b : {&ctx->h_stage, &ctx->h_rcv_ops[0], &ctx->h_rcv_ops[1], &ctx->h_out, &ctx->h_tok, &ctx->h_tokd[0],
-                         &ctx->h_tokd[1], &ctx->h_sums, &ctx->h_sumsd, &ctx->h_tokb, &ctx->h_tokb_runs, &ctx->h_rmd5})
+                         &ctx->h_tokd[1], &ctx->h_sums, &ctx->h_sumsd, &ctx->h_tokb, &ctx->h_tokb_runs, &ctx->h_rmd5,
+                         &ctx->h_md5_lanes, &ctx->h_md5_out})
         b->release();
     if (ctx->h_win.cap > (1u << 20)) ctx->h_win.release();  // (a Receiver pass's pieces; the scan's windows are small)
     // The batched scan's state stays: its chunk index, hit map, descriptors, pinned event and
@@ -594,12 +596,15 @@ int rsh_debug_k1_plan_batch(const uint64_t* addr, const uint64_t* lo, const uint
 }
 
 int rsh_debug_kernel_ms(rsh_ctx* ctx, int32_t which, double* ms) {
-    if (!ctx || !ms || which < 0 || which > 3) return RSH_E_INVAL;
+    if (!ctx || !ms || which < 0 || which > 4) return RSH_E_INVAL;
     *ms = -1.0;
-    const bool timed = which == 0 ? ctx->gen_timed : which == 1 ? ctx->spec_timed : which == 2 ? ctx->sums_timed : ctx->pm_timed;
+    const bool timed = which == 0 ? ctx->gen_timed : which == 1 ? ctx->spec_timed : which == 2 ? ctx->sums_timed
+                       : which == 3 ? ctx->pm_timed : ctx->md5_timed;
     if (!timed) return RSH_OK;
-    const hipEvent_t a = which == 0 ? ctx->ev_gen_a : which == 1 ? ctx->ev_k1a : which == 2 ? ctx->ev_sums_a : ctx->ev_pma;
-    const hipEvent_t b = which == 0 ? ctx->ev_gen_b : which == 1 ? ctx->ev_k1b : which == 2 ? ctx->ev_sums_b : ctx->ev_pmb;
+    const hipEvent_t a = which == 0 ? ctx->ev_gen_a : which == 1 ? ctx->ev_k1a : which == 2 ? ctx->ev_sums_a
+                         : which == 3 ? ctx->ev_pma : ctx->ev_md5_a;
+    const hipEvent_t b = which == 0 ? ctx->ev_gen_b : which == 1 ? ctx->ev_k1b : which == 2 ? ctx->ev_sums_b
+                         : which == 3 ? ctx->ev_pmb : ctx->ev_md5_b;
     RSH_HIP(hipSetDevice(ctx->device));
     RSH_HIP(hipEventSynchronize(b));
     float f = 0.f;

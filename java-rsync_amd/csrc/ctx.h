@@ -15,6 +15,7 @@
 
 #include "device.h"
 #include "hit_cache.h"
+#include "md5_file.h"
 #include "options.h"
 #include "phase_map.h"
 #include "resolver.h"
@@ -86,6 +87,32 @@ struct SumsUnframeWork {
 int sums_unframe_files(rsh_ctx* ctx, const SumsUnframeWork* w, size_t n);
 // ... and the same on the host, record by record (a file scanned tiled keeps its table in host memory)
 void sums_unframe_host(const rsh_header& h, const uint8_t* records, int32_t* weak, uint8_t* strong);
+// md5_device.cpp: the whole-file MD5s of files in HBM with file_md5_kernel, for a caller that holds the context's
+// claim.  start() closes what needs no lane and puts the first launch on the stream; finish() waits for it, takes its
+// results and runs the launches after it (stop_after >= 0: at most that many in all), so that a caller can work on
+// another stream between the two.  fs, closed and md5 (16 bytes per file) are the files' states before and after.
+class Md5DeviceRun {
+  public:
+    Md5DeviceRun(rsh_ctx* c, hipStream_t s, std::vector<const uint8_t*> data, std::vector<int64_t> n, int64_t slice);
+    ~Md5DeviceRun();  // waits for a launch that finish() did not take
+    int start();
+    int finish(int32_t stop_after = -1);
+    std::vector<Md5FileState> fs;
+    std::vector<char> closed;
+    std::vector<uint8_t> md5;
+    int32_t launches = 0;
+
+  private:
+    int enqueue();
+    rsh_ctx* c_;
+    hipStream_t s_;
+    std::vector<const uint8_t*> data_;
+    std::vector<int64_t> n_;
+    int64_t slice_;
+    std::vector<int32_t> order_;
+    std::vector<Md5Lane> lanes_;
+    bool pending_ = false;
+};
 }  // namespace rsh
 
 namespace rshi {
@@ -300,6 +327,12 @@ struct rsh_ctx {
     PinnedBuf h_tokb, h_tokb_runs, h_rmd5;
     hipEvent_t ev_sums_a = nullptr, ev_sums_b = nullptr;  // timing: the last sums kernel (rsh_debug_kernel_ms)
     bool sums_timed = false;
+    // rsh_file_md5_batch_device (md5_device.cpp): a launch's lanes and results in HBM, their pinned host sides, and the
+    // last file_md5_kernel launch's dispatch events (rsh_debug_kernel_ms)
+    DevBuf md5_lanes, md5_out;
+    PinnedBuf h_md5_lanes, h_md5_out;
+    hipEvent_t ev_md5_a = nullptr, ev_md5_b = nullptr;
+    bool md5_timed = false;
     std::atomic<bool> busy{false};   // the staging buffers and last_ev serve one call at a time
     rsh::BatchState* batch = nullptr;  // buffers of the batched (multi-file) entry points, on first use
     ~rsh_ctx() {
@@ -308,13 +341,13 @@ struct rsh_ctx {
                           &ph_weak[1], &ph_strong[1], &slots, &dslots,
                           &out, &first, &haw, &partials, &bucket, &seg_data, &seg_tab,
                           &rcv[0], &rcv[1], &rcv_ops[0], &rcv_ops[1], &prep_dev, &fc_dev, &sums_raw, &tok_runs, &tokb_runs, &tokb_outs,
-                          &pm_index, &pm_anchor, &pm_weak, &pm_strong, &pm_segs})
+                          &pm_index, &pm_anchor, &pm_weak, &pm_strong, &pm_segs, &md5_lanes, &md5_out})
             b->release();
         for (PinnedBuf* b : {&h_weak, &h_strong, &h_aw, &h_as, &h_fl, &h_pw[0], &h_ps[0], &h_pw[1], &h_ps[1], &h_lead, &h_pos, &h_out, &h_iv,
                              &h_tiles, &h_keys, &h_first, &h_win, &h_ptiles, &h_psegs, &h_hit, &h_win0, &h_pend, &h_bucket, &h_files,
                              &h_stage, &h_rcv_ops[0], &h_rcv_ops[1], &h_prep, &h_stamps, &h_fgw, &h_fjobs, &h_fout,
                              &h_tok, &h_tokd[0], &h_tokd[1], &h_sums, &h_sumsd, &h_runs, &h_untok, &h_tokb, &h_tokb_runs, &h_rmd5,
-                             &h_pm, &h_pmw, &h_pms, &h_pm_segs})
+                             &h_pm, &h_pmw, &h_pms, &h_pm_segs, &h_md5_lanes, &h_md5_out})
             b->release();
         if (abort_word) (void)hipFree(abort_word);
         if (ev_in) (void)hipEventDestroy(ev_in);
@@ -325,7 +358,7 @@ struct rsh_ctx {
         if (ev_flags) (void)hipEventDestroy(ev_flags);
         if (ev_prep) (void)hipEventDestroy(ev_prep);
         for (hipEvent_t e : {ev_k1a, ev_k1b, ev_gen_a, ev_gen_b, ev_rs_tail, ev_tok[0], ev_tok[1], ev_sums_a, ev_sums_b,
-                             ev_pm, ev_pma, ev_pmb})
+                             ev_pm, ev_pma, ev_pmb, ev_md5_a, ev_md5_b})
             if (e) (void)hipEventDestroy(e);
         if (aux) (void)hipStreamDestroy(aux);
         if (phase) (void)hipStreamDestroy(phase);

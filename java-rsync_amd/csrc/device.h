@@ -391,6 +391,13 @@ struct SumsSpan;
 hipError_t launch_sums_frame(const SumsSpan* spans, uint32_t n, uint32_t max_len, hipStream_t s);
 hipError_t launch_sums_unframe(const SumsSpan* spans, uint32_t n, uint32_t max_len, hipStream_t s);
 hipError_t launch_warm_sums(hipStream_t s);
+// Whole-file MD5s of files in HBM, one lane per file (device_md5.hip, md5_file.h): nwaves x 64 lanes (device memory),
+// lane k's 16 result bytes to out[16 k] (device memory).  start / stop (both or neither): events that take the
+// launch's own dispatch timestamps.
+struct Md5Lane;
+hipError_t launch_file_md5(const Md5Lane* lanes, uint32_t nwaves, uint8_t* out, bool aligned16, hipStream_t s,
+                           hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+hipError_t launch_warm_md5(hipStream_t s);
 // Probe hashes of many files (slots cleared by the caller): keys[i] into slots/mask.
 struct TableEnt {
     unsigned long long* slots;

@@ -52,6 +52,12 @@ enum Opt : int {
                            // the source (phase_map.h; 2 is the measured setting); 0, the default: never -- the map is a
                            // bet on a scan that lives, and one that a poisoned digest ends early loses it
     OPT_K1_ANYB,           // 1: block lengths off a multiple of 128 (512 and up) take the coalesced any-B K1; 0: per lane
+    OPT_MD5_DEVICE_SLICE,  // rsh_file_md5_batch_device: bytes a launch advances one file by at most (a multiple of 128): it
+                           // bounds how long one launch runs on a shared machine (MD5_SLICE_NOTE below)
+    OPT_RESIDENT_MD5,      // rsh_receiver_combine_batch_resident's verify digests: 0 the host path (every byte downloaded),
+                           // 1 file_md5_kernel on the second stream, 2 split between the two by md5_plan (md5_file.h)
+    OPT_MD5_LANE_KBPS,     // md5_plan: what one lane of file_md5_kernel digests, in 1000 bytes per second
+    OPT_MD5_LINK_KBPS,     // ... and what the host path takes in (PCIe and the host's multi-buffer MD5), the same unit
     OPT_COUNT
 };
 
@@ -70,8 +76,14 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"fault_inject", 0},        {"tokens_span", 256LL << 10}, {"tokens_piece", 8LL << 20},
     {"sums_piece", 32LL << 20}, {"tokens_runs", 64LL << 10}, {"k1_dma", 1},
     {"k1_prio", 1},             {"tokens_runs_batch", 4096}, {"resident_md5_bytes", 1LL << 30},
-    {"scan_phase_map", 0},      {"k1_anyb", 1},
+    {"scan_phase_map", 0},      {"k1_anyb", 1},         {"md5_device_slice", 64LL << 20},
+    {"resident_md5", 0},        {"md5_lane_kbps", 52000}, {"md5_link_kbps", 27700000},
 };
+// MD5_SLICE_NOTE.  Measured with tools/md5_device_bench.py (profiles/md5_device/; DESIGN.md section 4, "Whole-file MD5s
+// on the device").  md5_lane_kbps: a lane of file_md5_kernel digests 75 MB/s with up to 8192 files on the chip and
+// 52 MB/s with all 131072 lanes resident (two waves share a SIMD's VALU); the planner takes the lower.  md5_link_kbps:
+// the host path (download + md5_files on 16 cores) took in 27.7 GB/s at 8192 files of 1 MiB, its best shape (5.8 GB/s
+// at 64 KiB files).  The default slice of 64 MiB per file and launch is 0.9 s at 75 MB/s and 1.3 s at 52 MB/s.
 
 inline const OptInfo* opt_info() { return kOpts; }
 

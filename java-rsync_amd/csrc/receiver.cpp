@@ -846,6 +846,46 @@ int digest_resident(rsh_ctx* c, rsh_resident_job* jobs, const std::vector<Md5Src
     return RSH_OK;
 }
 
+// Option resident_md5 = 1: every file's digest by file_md5_kernel where the bytes lie; 2: the files of at most
+// md5_plan's cut length by the kernel and the longer ones by the host path above.  The kernel goes on the context's
+// second stream behind the launches that placed the targets, the host path's copies run on the first beside it, and
+// both are joined before the call returns.
+int digest_resident_split(rsh_ctx* c, rsh_resident_job* jobs, const std::vector<Md5Src>& srcs) {
+    int64_t cut = INT64_MAX;
+    if (opt(OPT_RESIDENT_MD5) == 2) {
+        std::vector<int64_t> len;
+        for (const Md5Src& s : srcs) len.push_back(s.len);
+        cut = md5_plan(len.data(), (int32_t)len.size(), opt(OPT_MD5_LANE_KBPS), opt(OPT_MD5_LINK_KBPS)).cut;
+    }
+    std::vector<Md5Src> host;
+    std::vector<const uint8_t*> data;
+    std::vector<int64_t> n;
+    std::vector<int32_t> job;
+    for (const Md5Src& s : srcs) {
+        if (s.len > cut) {
+            host.push_back(s);
+            continue;
+        }
+        data.push_back(s.d);
+        n.push_back(s.len);
+        job.push_back(s.job);
+    }
+    RSH_HIP(hipEventRecord(c->ev_in, c->stream));  // the targets are placed
+    RSH_HIP(hipStreamWaitEvent(c->aux, c->ev_in, 0));
+    Md5DeviceRun run(c, c->aux, std::move(data), std::move(n), opt(OPT_MD5_DEVICE_SLICE));
+    const int rs = run.start();
+    if (rs != RSH_OK) return rs;
+    const int rh = host.empty() ? RSH_OK : digest_resident(c, jobs, host);
+    const int rf = run.finish();
+    if (rh != RSH_OK) return rh;
+    if (rf != RSH_OK) return rf;
+    for (size_t k = 0; k < job.size(); ++k) {
+        if (!run.closed[k]) return RSH_E_DEVICE;
+        memcpy(jobs[job[k]].res.md5, &run.md5[16 * k], 16);
+    }
+    return RSH_OK;
+}
+
 // The call with the context claimed: fin[i] = 1 once job i's status and result are final.
 int combine_batch_resident(rsh_ctx* c, rsh_resident_job* jobs, int32_t njobs, int32_t flags, std::vector<char>& fin) {
     std::vector<std::unique_ptr<ResFile>> files;
@@ -898,7 +938,7 @@ int combine_batch_resident(rsh_ctx* c, rsh_resident_job* jobs, int32_t njobs, in
     const int g = launch_resident(c, ops, spans);
     if (g != RSH_OK) return g;
     if (!(flags & RSH_COMBINE_NO_MD5)) {
-        const int d = digest_resident(c, jobs, srcs);
+        const int d = opt(OPT_RESIDENT_MD5) == 0 ? digest_resident(c, jobs, srcs) : digest_resident_split(c, jobs, srcs);
         if (d != RSH_OK) return d;
     }
     RSH_HIP(hipStreamSynchronize(c->stream));  // the descriptors are read until the launches are done

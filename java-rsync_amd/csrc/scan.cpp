@@ -114,6 +114,7 @@ hipError_t ctx_warm(rsh_ctx* c) {
     ok(rsh::launch_warm_tokens(c->stream));
     ok(rsh::launch_warm_sums(c->stream));
     ok(rsh::launch_warm_phase(c->stream));
+    ok(rsh::launch_warm_md5(c->stream));
     ok(scan_buffers_ensure(c, kC, kDl, kC, true));
     ok(prep_ensure(c, kLeadWindows + rsh::opt(rsh::OPT_SCAN_SAMPLES) + 1));
     constexpr size_t kSmall = 64 << 10;  // PinnedBuf's least allocation

@@ -184,6 +184,23 @@ class Md5Job(ctypes.Structure):
                 ("md5", ctypes.c_uint8 * 16)]
 
 
+class Md5DeviceJob(ctypes.Structure):
+    """rsh_md5_device_job: one file of rsh_file_md5_batch_device (device bytes, any alignment)."""
+    _fields_ = [("d_data", ctypes.c_void_p), ("n", ctypes.c_int64), ("md5", ctypes.c_uint8 * 16),
+                ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class Md5SelftestJob(ctypes.Structure):
+    """rsh_md5_selftest_job: one file of rsh_debug_md5_device_selftest, with the chain's state going in and out."""
+    _fields_ = [("data", ctypes.c_void_p), ("n", ctypes.c_int64), ("state", ctypes.c_uint32 * 4),
+                ("done", ctypes.c_int64), ("md5", ctypes.c_uint8 * 16), ("closed", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+MD5_INIT = (0x67452301, 0xefcdab89, 0x98badcfe, 0x10325476)
+MD5_EMPTY = bytes.fromhex("d41d8cd98f00b204e9800998ecf8427e")
+
+
 class TokenRun(ctypes.Structure):
     """rsh_token_run: one record of the token walk's run list (rsh_debug_tokens_scan_selftest)."""
     _fields_ = [("pos", ctypes.c_int64), ("kind", ctypes.c_int32), ("value", ctypes.c_int32),
@@ -214,7 +231,7 @@ EXPORTS = ["rsh_abi_version", "rsh_strerror", "rsh_last_error", "rsh_device_coun
            "rsh_sums_wire_size", "rsh_header_from_wire", "rsh_sums_frame_device", "rsh_sums_unframe_device",
            "rsh_block_sums_batch_wire", "rsh_match_scan_batch_wire", "rsh_block_sums_batch_wire_multi",
            "rsh_match_scan_batch_wire_multi", "rsh_tokens_frame_device", "rsh_receiver_combine_resident",
-           "rsh_tokens_frame_batch_device", "rsh_receiver_combine_batch_resident"]
+           "rsh_tokens_frame_batch_device", "rsh_receiver_combine_batch_resident", "rsh_file_md5_batch_device"]
 # include/rsync_hip_debug.h (testing / diagnostics ABI)
 DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_reset_options", "rsh_debug_k1_clock",
                  "rsh_debug_streams_busy", "rsh_debug_kernel_ms", "rsh_debug_multi_selftest", "rsh_debug_generation",
@@ -222,7 +239,8 @@ DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_rese
                  "rsh_debug_untokens_selftest", "rsh_debug_k1_dma_swizzle", "rsh_debug_k1_wave_times",
                  "rsh_debug_tokens_scan_batch_selftest", "rsh_debug_phase_plan", "rsh_debug_phase_map_selftest",
                  "rsh_debug_phase_round_b", "rsh_debug_phase_segments", "rsh_debug_k1_plan",
-                 "rsh_debug_k1_plan_batch"]
+                 "rsh_debug_k1_plan_batch", "rsh_debug_md5_device_selftest", "rsh_debug_md5_closing",
+                 "rsh_debug_md5_plan"]
 
 _LIB = None
 
@@ -358,6 +376,12 @@ def lib():
         "rsh_debug_phase_map_selftest": ([P, P, I64, I32, P, I32, P, I64, I32, P, P], ctypes.c_int),
         "rsh_debug_phase_round_b": ([P, P, I64, I64, I32, I64, P, I64, ctypes.POINTER(I64)], ctypes.c_int),
         "rsh_debug_phase_segments": ([P, P, I64, I64, I64, I32, I32, I64, P, I64, ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_file_md5_batch_device": ([P, ctypes.POINTER(Md5DeviceJob), I32], ctypes.c_int),
+        "rsh_debug_md5_device_selftest": ([P, ctypes.POINTER(Md5SelftestJob), I32, I64, I32, ctypes.POINTER(I32)],
+                                          ctypes.c_int),
+        "rsh_debug_md5_closing": ([P, I32, I64, P, ctypes.POINTER(I32)], ctypes.c_int),
+        "rsh_debug_md5_plan": ([P, P, I32, I64, I64, I64, P, ctypes.POINTER(I32), P, ctypes.POINTER(I64),
+                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         if os.environ.get("RSH_LIB") and name in DEBUG_EXPORTS and not hasattr(L, name):
@@ -566,6 +590,54 @@ def untokens_selftest(tokens, length, pos, T, count, out, span=0, ctx=None):
     return nd.value, lo.value, hi.value
 
 
+def md5_device_selftest(jobs, slice_bytes=0, stop_after=-1, ctx=None):
+    """rsh_debug_md5_device_selftest: whole-file MD5s one lane per file.  jobs = [(data, n[, state, done])]: ctx None,
+    data is a uint8 array or a host address and the host stand-in runs; with a Context, a DeviceBuffer or device address
+    and file_md5_kernel runs.  state (four words) and done: where the chain resumes (default: a fresh file); only the
+    bytes from data + done on are read.  slice_bytes: what a launch advances a file by at most (0: option
+    md5_device_slice); stop_after: at most that many launches (-1: until every file is closed).
+    -> ([(closed, digest or None, state, done)], launches)."""
+    n = len(jobs)
+    sj = (Md5SelftestJob * max(n, 1))()
+    for i, job in enumerate(jobs):
+        sj[i].data, sj[i].n = _addr(job[0]).value, job[1]
+        sj[i].state[:] = list(job[2]) if len(job) > 2 else list(MD5_INIT)
+        sj[i].done = job[3] if len(job) > 3 else 0
+    made = ctypes.c_int32()
+    _check(lib().rsh_debug_md5_device_selftest(None if ctx is None else ctx.handle, sj, n, slice_bytes, stop_after,
+                                               ctypes.byref(made)))
+    return [(bool(sj[i].closed), bytes(sj[i].md5) if sj[i].closed else None, tuple(sj[i].state), sj[i].done)
+            for i in range(n)], made.value
+
+
+def md5_closing(tail, n):
+    """rsh_debug_md5_closing: the 1, 2 or 3 final 64-byte blocks for the r = len(tail) < 128 bytes that end a file of n
+    bytes, as one bytes object."""
+    t = np.frombuffer(bytes(tail), np.uint8)
+    out = np.zeros(192, np.uint8)
+    nblk = ctypes.c_int32()
+    _check(lib().rsh_debug_md5_closing(_ptr(t) if t.size else None, t.size, n, _ptr(out), ctypes.byref(nblk)))
+    return out[:64 * nblk.value].tobytes()
+
+
+def md5_plan(lengths, done=None, slice_bytes=0, lane_kbps=0, link_kbps=0):
+    """rsh_debug_md5_plan: the next launch's grouping of files of these lengths (done: bytes already digested per file,
+    default none) and the planner's cut at the given rates in 1000 bytes per second (0: the options) ->
+    dict(order=[file indices, 64 to a wave], wave_nst=[stages per wave], cut=length or -1, t_dev=, t_host= seconds)."""
+    n = np.ascontiguousarray(lengths, dtype=np.int64)
+    d = None if done is None else np.ascontiguousarray(done, dtype=np.int64)
+    order = np.zeros(max(n.size, 1), np.int32)
+    waves = np.zeros(max((n.size + 63) // 64, 1), np.uint32)
+    n_order, cut = ctypes.c_int32(), ctypes.c_int64()
+    td, th = ctypes.c_double(), ctypes.c_double()
+    _check(lib().rsh_debug_md5_plan(_ptr(n) if n.size else None, _ptr(d), n.size, slice_bytes, lane_kbps, link_kbps,
+                                    _ptr(order), ctypes.byref(n_order), _ptr(waves), ctypes.byref(cut),
+                                    ctypes.byref(td), ctypes.byref(th)))
+    k = n_order.value
+    return dict(order=[int(x) for x in order[:k]], wave_nst=[int(x) for x in waves[:(k + 63) // 64]], cut=cut.value,
+                t_dev=td.value, t_host=th.value)
+
+
 def sums_wire_size(h):
     """rsh_sums_wire_size: the bytes of a file's header + table on the Generator's channel."""
     return lib().rsh_sums_wire_size(ctypes.byref(h))
@@ -723,7 +795,8 @@ class Context:
 
     def kernel_ms(self, which):
         """The last Generator (0) or speculation (1) K1's duration from its own dispatch events, the last sums kernel's
-        (2) or the last phase_map_selftest's kernel launch (3) from events around it (-1: not timed)."""
+        (2) or the last phase_map_selftest's kernel launch (3) from events around it, the last file_md5_kernel launch's
+        (4) from its own dispatch events (-1: not timed)."""
         ms = ctypes.c_double(-1.0)
         _check(lib().rsh_debug_kernel_ms(self._p, which, ctypes.byref(ms)))
         return ms.value
@@ -1016,6 +1089,15 @@ class Context:
             j.defer_write = int(bool(job[7])) if len(job) > 7 else 0
         rc = lib().rsh_receiver_combine_batch_resident(self._p, rj, len(jobs), flags)
         return rc, [(rj[i].status, CombineResult.from_buffer_copy(rj[i].res)) for i in range(len(jobs))]
+
+    def file_md5_batch_device(self, files):
+        """rsh_file_md5_batch_device: the whole-file MD5s of many files in HBM, one lane of file_md5_kernel each.
+        files = [(DeviceBuffer or device address, n)] -> (the call's status, [(status, digest)]).  Nothing is raised."""
+        mj = (Md5DeviceJob * max(len(files), 1))()
+        for i, (d, n) in enumerate(files):
+            mj[i].d_data, mj[i].n = _addr(d).value, n
+        rc = lib().rsh_file_md5_batch_device(self._p, mj, len(files))
+        return rc, [(mj[i].status, bytes(mj[i].md5)) for i in range(len(files))]
 
     def tokens_frame_batch_device(self, jobs):
         """rsh_tokens_frame_batch_device: a segment's streams framed into device memory in one call.
