@@ -181,6 +181,32 @@ int rsh_debug_tokens_scan_batch_selftest(rsh_ctx* ctx, rsh_token_scan_job* jobs,
 int rsh_debug_untokens_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t pos, int32_t T,
                                 int64_t count, uint8_t* out, int64_t span, int64_t* n_desc, int64_t* lo, int64_t* hi);
 
+/* The byte movers of device_io.hip through their production launchers (device.h), unchanged, on the context's stream,
+ * which is synchronised before the call returns; no kernel of the entry's own.  ops: a host array of n >= 1 ranges of
+ * device memory, len >= 0.  form 0: launch_gather_ops with the ops in pinned host memory (the single-file Receivers);
+ * 1: launch_gather_ops with the ops uploaded to device memory (the segment Receiver); 2: launch_copy_few (n <= 4);
+ * 3: launch_copy_many at high priority; 4: launch_copy_many in the background form (one workgroup per range);
+ * 5: launch_copy_to_host (n == 1).  avg_len goes to launch_gather_ops as it is (the 256- or 1024-thread form) and is
+ * ignored by the other forms.  Every destination is device memory: the kernels do not tell device memory from pinned
+ * host memory, which is where the production callers of forms 2 to 5 point them.  Forms 3 to 5 write with 16-byte
+ * stores from the destination's first byte (copy_piece): RSH_E_INVAL, and no launch, unless every destination is
+ * 16-byte aligned. */
+typedef struct {
+    const void* src;
+    void* dst;
+    int64_t len;
+} rsh_io_op;
+int rsh_debug_io_selftest(rsh_ctx* ctx, int32_t form, const rsh_io_op* ops, int32_t n, int64_t avg_len);
+
+/* launch_window_weak over the positions p[0, count) (each in [0, n)) of the one file d_data[0, n) in device memory:
+ * the weak sum of the window [p, p + min(block_length, n - p)), one workgroup per position.  by_block = 0: the sum of
+ * p[i] to out[i].  by_block = 1: to out[p[i] / block_length], the form that fills ScanFile::aligned_weak -- every
+ * position a multiple of block_length (else RSH_E_INVAL), out holds ceil(n / block_length) words, and a word no
+ * position names keeps the value it had on entry.  out is host memory, copied to and from the pinned buffer the
+ * kernel writes. */
+int rsh_debug_window_weak_selftest(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t block_length, const int64_t* p,
+                                   int32_t count, int32_t by_block, int32_t* out);
+
 /* The phase map of a single-file scan (option scan_phase_map = k > 0: once k phase-shifted speculations have gone out,
  * the next hint that nothing covers maps the rest of the source; 0, the default: never).  A sample at position a keys
  * the positions [a, a + 2 B) whose window is full and looks them up in the table; its anchor is the smallest p in

@@ -119,11 +119,13 @@ hipError_t SegmentLayout::plan(BatchState* S, const std::vector<FileLayout*>& fi
         fs.na = (fs.n + fs.B - 1) / fs.B;
         fs.nf = std::min<int64_t>(fs.na, fs.C);
         fs.ns = pow2_at_least(2 * (uint64_t)fs.C + 2);
-        fs.off_tw = tw, tw += fs.C;
-        fs.off_ts = ts, ts += (int64_t)fs.C * fs.dl;
-        fs.off_na = tna, tna += fs.na;
-        fs.off_as = tas, tas += fs.na * fs.dl;
-        fs.off_nf = tnf, tnf += fs.nf;
+        // every file's part starts on a 16-byte boundary (tw, tna count words): the parts of h_weak, h_strong, h_aw,
+        // h_as and h_fl are destinations of launch_copy_many, whose 16-byte stores start at a destination's first byte
+        fs.off_tw = tw, tw += pad16((int64_t)fs.C * 4) / 4;
+        fs.off_ts = ts, ts += pad16((int64_t)fs.C * fs.dl);
+        fs.off_na = tna, tna += pad16(fs.na * 4) / 4;
+        fs.off_as = tas, tas += pad16(fs.na * fs.dl);
+        fs.off_nf = tnf, tnf += pad16(fs.nf);
         fs.off_ns = tns, tns += fs.ns;
         fs.off_hit = thit, thit += pad16(16 + fs.B);  // one window per file (ScanFile::nwin = 1)
         fs.off_w0 = tw0, tw0 += pad16(std::min<int64_t>(fs.B, fs.n));

@@ -330,7 +330,8 @@ struct GatherEnt {
 hipError_t launch_gather_bytes(const ScanFile* files, const GatherEnt* ents, uint32_t n, uint8_t* out, hipStream_t s);
 // True weak sums at arbitrary positions: Rolling.compute(data + p, min(B, n - p)).
 hipError_t launch_window_weak(const ScanFile* files, const GatherEnt* ents, uint32_t n, int32_t* out, hipStream_t s);
-// Many device ranges into pinned host memory (or device memory), one kernel.
+// Many device ranges into pinned host memory (or device memory), one kernel.  Every dst must be 16-byte aligned: the
+// kernel writes 16-byte pieces from dst on (copy_piece, one store each); src and len are free.
 struct CopyEnt {
     const uint8_t* src;
     uint8_t* dst;
@@ -344,9 +345,11 @@ struct CopyFew {
     uint32_t n;
 };
 hipError_t launch_copy_few(const CopyFew& f, hipStream_t s);
-// The same ranges by one workgroup, then `gen` into the pinned `stamp` (the host spins on it).
+// The same ranges by one workgroup, then `gen` into the pinned `stamp` (the host spins on it).  Unlike launch_copy_few
+// it copies no byte-wise head: every dst must be 16-byte aligned (copy_piece), as for launch_copy_many.
 hipError_t launch_copy_few_stamped(const CopyFew& f, int* stamp, int gen, hipStream_t s);
-// n bytes of device memory into pinned host memory (h_dst 16-byte aligned), by a kernel.
+// n bytes of device memory into pinned host memory, by a kernel.  h_dst must be 16-byte aligned (copy_piece's 16-byte
+// stores from h_dst on); d_src and n are free.
 hipError_t launch_copy_to_host(const uint8_t* d_src, int64_t n, uint8_t* h_dst, hipStream_t s);
 // Byte ranges between arbitrary (unaligned) device addresses: one op per workgroup, 16-byte stores to
 // the aligned middle of each destination (Receiver block gather).

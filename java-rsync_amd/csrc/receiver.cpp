@@ -1114,6 +1114,84 @@ int rsh_debug_untokens_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tok
     return RSH_OK;
 }
 
+// The destinations are device memory here and pinned host memory in most production calls of forms 2 to 5: the
+// kernels do not tell the two apart (they store through a flat address either way).
+int rsh_debug_io_selftest(rsh_ctx* ctx, int32_t form, const rsh_io_op* ops, int32_t n, int64_t avg_len) {
+    static_assert(sizeof(rsh_io_op) == sizeof(GatherOp) && sizeof(rsh_io_op) == sizeof(CopyEnt) &&
+                      offsetof(rsh_io_op, dst) == offsetof(GatherOp, dst) && offsetof(rsh_io_op, len) == offsetof(GatherOp, len) &&
+                      offsetof(rsh_io_op, dst) == offsetof(CopyEnt, dst) && offsetof(rsh_io_op, len) == offsetof(CopyEnt, len),
+                  "rsh_io_op is GatherOp is CopyEnt");
+    if (!ctx || !ops || n < 1 || form < 0 || form > 5) return RSH_E_INVAL;
+    if ((form == 2 && n > 4) || (form == 5 && n != 1)) return RSH_E_INVAL;
+    int64_t max_len = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        if (ops[i].len < 0 || (ops[i].len > 0 && (!ops[i].src || !ops[i].dst))) return RSH_E_INVAL;
+        // copy_piece's contract (forms 3 to 5): 16-byte stores from the destination's first byte
+        if (form >= 3 && (reinterpret_cast<uintptr_t>(ops[i].dst) & 15) != 0) return RSH_E_INVAL;
+        max_len = std::max(max_len, ops[i].len);
+    }
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * sizeof(rsh_io_op);
+    RSH_HIP(ctx->h_pos.ensure(bytes));
+    memcpy(ctx->h_pos.p, ops, bytes);
+    switch (form) {
+        case 0:
+            RSH_HIP(launch_gather_ops(ctx->h_pos.as<GatherOp>(), (uint32_t)n, ctx->stream, avg_len));
+            break;
+        case 1:
+            RSH_HIP(ctx->rcv_ops[0].ensure(bytes + 16));
+            RSH_HIP(hipMemcpyAsync(ctx->rcv_ops[0].p, ctx->h_pos.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+            RSH_HIP(launch_gather_ops(ctx->rcv_ops[0].as<GatherOp>(), (uint32_t)n, ctx->stream, avg_len));
+            break;
+        case 2: {
+            CopyFew f{};
+            f.n = (uint32_t)n;
+            memcpy(f.e, ops, (size_t)n * sizeof(CopyEnt));  // (the same fields: the static_assert above)
+            RSH_HIP(launch_copy_few(f, ctx->stream));
+            break;
+        }
+        case 3:
+        case 4:
+            RSH_HIP(launch_copy_many(ctx->h_pos.as<CopyEnt>(), (uint32_t)n, max_len, ctx->stream, form == 4));
+            break;
+        default:
+            RSH_HIP(launch_copy_to_host(static_cast<const uint8_t*>(ops[0].src), ops[0].len,
+                                        static_cast<uint8_t*>(ops[0].dst), ctx->stream));
+            break;
+    }
+    RSH_HIP(hipStreamSynchronize(ctx->stream));  // the descriptors are read until the launch is done
+    return RSH_OK;
+}
+
+int rsh_debug_window_weak_selftest(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t block_length, const int64_t* p,
+                                   int32_t count, int32_t by_block, int32_t* out) {
+    if (!ctx || !d_data || n < 1 || block_length < 1 || !p || count < 1 || !out) return RSH_E_INVAL;
+    const int64_t B = block_length, nblocks = (n + B - 1) / B;
+    for (int32_t i = 0; i < count; ++i)
+        if (p[i] < 0 || p[i] >= n || (by_block && p[i] % B != 0)) return RSH_E_INVAL;
+    const size_t nout = by_block ? (size_t)nblocks : (size_t)count;
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    RSH_HIP(ctx->h_files.ensure(sizeof(ScanFile)));
+    RSH_HIP(ctx->h_pos.ensure((size_t)count * sizeof(GatherEnt)));
+    RSH_HIP(ctx->h_out.ensure(nout * sizeof(int32_t)));
+    int32_t* h_out = ctx->h_out.as<int32_t>();
+    memcpy(h_out, out, nout * sizeof(int32_t));
+    ScanFile* F = ctx->h_files.as<ScanFile>();
+    memset(F, 0, sizeof(ScanFile));
+    F->data = static_cast<const uint8_t*>(d_data);
+    F->n = n;
+    F->B = (uint32_t)block_length;
+    F->aligned_weak = by_block ? h_out : nullptr;
+    GatherEnt* ents = ctx->h_pos.as<GatherEnt>();
+    for (int32_t i = 0; i < count; ++i) ents[i] = GatherEnt{p[i], 0, by_block ? 1 : 0};
+    RSH_HIP(launch_window_weak(F, ents, (uint32_t)count, by_block ? nullptr : h_out, ctx->stream));
+    RSH_HIP(hipStreamSynchronize(ctx->stream));
+    memcpy(out, h_out, nout * sizeof(int32_t));
+    return RSH_OK;
+}
+
 int rsh_receiver_combine_device(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, const rsh_header* h,
                                 const void* d_replica, int64_t replica_len, int32_t defer_write, void* d_target,
                                 int64_t target_cap, rsh_combine_result* out) {

@@ -240,7 +240,7 @@ DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_rese
                  "rsh_debug_tokens_scan_batch_selftest", "rsh_debug_phase_plan", "rsh_debug_phase_map_selftest",
                  "rsh_debug_phase_round_b", "rsh_debug_phase_segments", "rsh_debug_k1_plan",
                  "rsh_debug_k1_plan_batch", "rsh_debug_md5_device_selftest", "rsh_debug_md5_closing",
-                 "rsh_debug_md5_plan"]
+                 "rsh_debug_md5_plan", "rsh_debug_io_selftest", "rsh_debug_window_weak_selftest"]
 
 _LIB = None
 
@@ -380,6 +380,8 @@ def lib():
         "rsh_debug_md5_device_selftest": ([P, ctypes.POINTER(Md5SelftestJob), I32, I64, I32, ctypes.POINTER(I32)],
                                           ctypes.c_int),
         "rsh_debug_md5_closing": ([P, I32, I64, P, ctypes.POINTER(I32)], ctypes.c_int),
+        "rsh_debug_io_selftest": ([P, I32, P, I32, I64], ctypes.c_int),
+        "rsh_debug_window_weak_selftest": ([P, P, I64, I32, P, I32, I32, P], ctypes.c_int),
         "rsh_debug_md5_plan": ([P, P, I32, I64, I64, I64, P, ctypes.POINTER(I32), P, ctypes.POINTER(I64),
                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
     }
@@ -588,6 +590,37 @@ def untokens_selftest(tokens, length, pos, T, count, out, span=0, ctx=None):
     _check(lib().rsh_debug_untokens_selftest(None if ctx is None else ctx.handle, _addr(tokens), length, pos, T, count,
                                              _addr(out), span, ctypes.byref(nd), ctypes.byref(lo), ctypes.byref(hi)))
     return nd.value, lo.value, hi.value
+
+
+IO_GATHER_PINNED, IO_GATHER_DEVICE, IO_COPY_FEW, IO_COPY_MANY, IO_COPY_MANY_BG, IO_COPY_TO_HOST = range(6)
+IO_OP_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<i8")])  # rsh_io_op
+
+
+def io_selftest(ctx, form, ops, avg_len=0):
+    """rsh_debug_io_selftest: one launch of a byte mover of device_io.hip through its production launcher over
+    ops = [(src, dst, len)] (device addresses), the context's stream synchronised afterwards: the status, not raised.
+    form: IO_GATHER_PINNED / IO_GATHER_DEVICE (launch_gather_ops with the ops in pinned host / device memory; avg_len
+    chooses the 256- or the 1024-thread form), IO_COPY_FEW (at most 4 ops), IO_COPY_MANY, IO_COPY_MANY_BG,
+    IO_COPY_TO_HOST (one op); the last three need 16-byte aligned destinations (RSH_E_INVAL otherwise)."""
+    a = np.array([tuple(int(v) for v in op) for op in ops], dtype=IO_OP_DTYPE)
+    return lib().rsh_debug_io_selftest(ctx.handle, form, _ptr(a) if a.size else None, a.size, avg_len)
+
+
+def window_weak_selftest(ctx, d_data, n, block_length, positions, by_block=False, out=None):
+    """rsh_debug_window_weak_selftest: window_weak_kernel's sums of the windows [p, p + min(block_length, n - p)) of
+    the file d_data[0, n) (a DeviceBuffer or device address), as an int32 array.  by_block False: one sum per
+    position, in order.  True: the positions are multiples of block_length and the sum of p lands in word
+    p / block_length of `out` (int32, ceil(n / block_length) words; the other words keep their values)."""
+    p = np.ascontiguousarray(positions, dtype=np.int64)
+    if by_block:
+        res = np.ascontiguousarray(out, dtype=np.int32).copy()
+        if res.size != -(-n // block_length):
+            raise ValueError("out holds one word per block")
+    else:
+        res = np.zeros(max(p.size, 1), np.int32)
+    _check(lib().rsh_debug_window_weak_selftest(ctx.handle, _addr(d_data), n, block_length, _ptr(p) if p.size else None,
+                                                p.size, int(bool(by_block)), _ptr(res)))
+    return res if by_block else res[:p.size]
 
 
 def md5_device_selftest(jobs, slice_bytes=0, stop_after=-1, ctx=None):
