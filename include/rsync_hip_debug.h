@@ -8,7 +8,12 @@
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
  * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio, tokens_runs_batch, resident_md5_bytes,
- * scan_phase_map, k1_anyb, md5_device_slice, resident_md5, md5_lane_kbps, md5_link_kbps.
+ * scan_phase_map, k1_anyb, md5_device_slice, resident_md5, md5_lane_kbps, md5_link_kbps, tokens_cycle.
+ *
+ * tokens_cycle = 1: the resident Receivers' token walk (token_scan_kernel, token_scan_batch_kernel) proves whole cycles
+ * of runs per lane where a pass's records repeat a cycle of 2 to 4 records (the half-modified file's match token and
+ * literal token in turn); 0 (default): one run per round, the kernels' instantiation without the cycle round.  The
+ * records, positions and statuses are identical in both.
  *
  * resident_md5 = 0 (default): the segment Receiver's verify digests come down to the host; 1: file_md5_kernel digests
  * every finished file where it lies, on the context's second stream; 2: the files up to the planner's length cut on the
@@ -152,13 +157,19 @@ typedef struct {
 } rsh_token_run;
 int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
                                    rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status);
+/* The same pass, and what it took: *rounds the memory round trips of the walk (plain rounds plus cycle attempts, option
+ * tokens_cycle), *cycles the cycles that cycle rounds proved (either may be NULL). */
+int rsh_debug_tokens_scan_rounds_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
+                                          rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status,
+                                          int64_t* rounds, int64_t* cycles);
 
 /* The segment's walk, token_scan_batch_kernel: one pass over the files live[0, nlive) (distinct indices into jobs), each
  * from its own `from` into its own `runs` (cap records, 1 .. 2^24), a workgroup per file.  ctx == NULL: tokens and runs
  * are host memory and the host stand-in runs a round of `lanes` lanes (a multiple of 64 up to 1024; 0: the kernel's
  * width) -- 64 is the single-file walk's round.  Otherwise they are device memory and the kernel runs, all files in one
  * launch (lanes 0 or the kernel's width).  n_runs, pos and status as rsh_debug_tokens_scan_selftest's; a file that is
- * not in `live` gets -1 in all three (on the device: the bytes its entry held before the launch). */
+ * not in `live` gets -1 in all three (on the device: the bytes its entry held before the launch).  reserved: the pass's
+ * rounds, as rsh_debug_tokens_scan_rounds_selftest's (-1 for a file that did not walk). */
 typedef struct {
     const uint8_t* tokens;
     int64_t tokens_len;
@@ -168,7 +179,7 @@ typedef struct {
     int64_t n_runs;   /* out */
     int64_t pos;      /* out */
     int32_t status;   /* out */
-    int32_t reserved;
+    int32_t reserved; /* out: rounds */
 } rsh_token_scan_job;
 int rsh_debug_tokens_scan_batch_selftest(rsh_ctx* ctx, rsh_token_scan_job* jobs, int32_t njobs, const int32_t* live,
                                          int32_t nlive, int32_t lanes);

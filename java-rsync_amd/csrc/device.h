@@ -374,18 +374,19 @@ hipError_t launch_token_frame(const TokSpan* spans, uint32_t n, uint32_t max_len
 struct TokRun;
 struct TokScanOut;
 struct UntokSpan;
+// cycle: option tokens_cycle (cycle rounds are attempted); cycles (device memory, or null): the cycles they proved.
 hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
-                             hipStream_t s);
+                             int32_t cycle, int64_t* cycles, hipStream_t s);
 hipError_t launch_token_unframe(const UntokSpan* spans, uint32_t n, uint32_t max_len, hipStream_t s);
 // A segment's walk: one workgroup per entry of live[0, nlive), each an index into jobs (both in pinned host memory);
 // file j's TokScanOut goes to outs[j] (device memory), its records where its descriptor says.
 struct TokScanJob;
 hipError_t launch_token_scan_batch(const TokScanJob* jobs, const int32_t* live, uint32_t nlive, TokScanOut* outs,
-                                   hipStream_t s);
+                                   int32_t cycle, hipStream_t s);
 #ifdef RSH_KBENCH
 // (kbench: the round's width in waves, 1, 4, 8 or 16)
 hipError_t launch_token_scan_batch_variant(uint32_t waves, const TokScanJob* jobs, const int32_t* live, uint32_t nlive,
-                                           TokScanOut* outs, hipStream_t s);
+                                           TokScanOut* outs, int32_t cycle, hipStream_t s);
 #endif
 hipError_t launch_warm_tokens(hipStream_t s);
 // The checksum table between SoA and wire form (device_sums.hip, sums_frame.h): spans in device or pinned host

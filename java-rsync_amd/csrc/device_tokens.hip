@@ -178,9 +178,13 @@ hipError_t launch_token_unframe(const UntokSpan* spans, uint32_t n, uint32_t max
 }
 
 // One wave walks the stream from `from` (token_scan.h tok_scan_walk): every lane runs the same control flow over
-// wave-uniform values, lane 0 stores the records.
+// wave-uniform values, lane 0 stores the records.  A cycle round (option tokens_cycle): lane k checks cycle k, the
+// ballot's leading lanes are the cycles proven, each of those lanes stores its own records, and the last one's first
+// int comes back by a lane read.
+template <bool kCycle>
 __global__ __launch_bounds__(kScanLanes) void token_scan_kernel(const uint8_t* __restrict__ tokens, int64_t len, int64_t from,
-                                                               TokRun* __restrict__ runs, int64_t cap, TokScanOut* __restrict__ out) {
+                                                               TokRun* __restrict__ runs, int64_t cap, TokScanOut* __restrict__ out,
+                                                               int64_t* __restrict__ cycles) {
     typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
     const GlobalByte base = (GlobalByte)(uintptr_t)tokens;
     const uint32_t lane = threadIdx.x;
@@ -197,12 +201,21 @@ __global__ __launch_bounds__(kScanLanes) void token_scan_kernel(const uint8_t* _
         const uint32_t part = L < kScanLanes ? (uint32_t)__shfl((int)c, (int)L) : 0u;    // the first other lane's ints
         return (int64_t)__builtin_amdgcn_readfirstlane((int)(per * L + part));
     };
-    tok_scan_walk(head, round, len, from, runs, cap, lane == 0, out);
+    auto cycle = [&](const TokCycle& T, int64_t pos, int64_t n, int32_t* x0) -> int64_t {
+        const TokCycleLane c = tok_cycle_lane(ld, T, pos, len, lane);
+        const unsigned long long full = __ballot(c.ok);
+        const uint32_t m = full == ~0ull ? kScanLanes : (uint32_t)__builtin_ctzll(~full);  // leading proven cycles
+        if (lane < m) tok_cycle_store(T, c, pos, lane, runs + n, lane + 1 == m);
+        *x0 = __builtin_amdgcn_readfirstlane(__shfl(c.last, m > 0 ? (int)m - 1 : 0));
+        return (int64_t)__builtin_amdgcn_readfirstlane((int)m);
+    };
+    tok_scan_walk<kCycle>(head, round, cycle, len, from, runs, cap, lane == 0, out, cycles);
 }
 
 hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
-                             hipStream_t s) {
-    hipLaunchKernelGGL(token_scan_kernel, dim3(1), dim3(kScanLanes), 0, s, tokens, len, from, runs, cap, out);
+                             int32_t cycle, int64_t* cycles, hipStream_t s) {
+    if (cycle) hipLaunchKernelGGL(token_scan_kernel<true>, dim3(1), dim3(kScanLanes), 0, s, tokens, len, from, runs, cap, out, cycles);
+    else hipLaunchKernelGGL(token_scan_kernel<false>, dim3(1), dim3(kScanLanes), 0, s, tokens, len, from, runs, cap, out, cycles);
     return hipGetLastError();
 }
 
@@ -212,13 +225,17 @@ hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, T
 // workgroup: head(pos) reads one address in every lane, and a round's result comes out of LDS.  A round writes the
 // pair buffer the round before it did not, so one barrier per round is enough: a wave can only be two rounds ahead
 // of another after that one has passed the barrier between them.  Thread 0 stores the records and the TokScanOut.
-template <uint32_t W>
+// A cycle round (option tokens_cycle) is a round like the others -- one barrier, the other pair buffer -- with thread
+// 64 w + i on cycle 64 w + i: beside its pair a wave leaves the first int of the last record of its last leading lane,
+// which is the round's last proven cycle when the count ends in that wave.
+template <uint32_t W, bool kCycle>
 __global__ __launch_bounds__(kScanLanes * W) void token_scan_batch_kernel(const TokScanJob* __restrict__ jobs,
                                                                          const int32_t* __restrict__ live,
                                                                          TokScanOut* __restrict__ outs) {
     typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
     typedef TokRun __attribute__((address_space(1))) * GlobalRuns;
     __shared__ uint32_t s_full[2][W], s_part[2][W];
+    __shared__ int32_t s_x0[2][W];
     const int32_t job = live[blockIdx.x];
     const TokScanJob J = jobs[job];
     const GlobalByte base = (GlobalByte)(uintptr_t)J.tokens;
@@ -247,25 +264,55 @@ __global__ __launch_bounds__(kScanLanes * W) void token_scan_batch_kernel(const 
         turn ^= 1u;
         return m;
     };
-    tok_scan_walk(head, round, len, J.from, runs, J.cap, tid == 0, outs + job);
+    auto cycle = [&](const TokCycle& T, int64_t pos, int64_t n, int32_t* x0) -> int64_t {
+        const TokCycleLane c = tok_cycle_lane(ld, T, pos, len, tid);
+        const unsigned long long full = __ballot(c.ok);
+        const uint32_t L = full == ~0ull ? kScanLanes : (uint32_t)__builtin_ctzll(~full);
+        const int32_t xl = __shfl(c.last, L > 0 ? (int)L - 1 : 0);
+        if (lane == 0) {
+            s_full[turn][wave] = L;
+            s_part[turn][wave] = 0u;
+            s_x0[turn][wave] = xl;
+        }
+        __syncthreads();
+        const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)tok_scan_combine(s_full[turn], s_part[turn], W, 1u));
+        if (tid < m) tok_cycle_store(T, c, pos, tid, runs + n, tid + 1 == m);
+        *x0 = __builtin_amdgcn_readfirstlane(s_x0[turn][m > 0 ? (m - 1) / kScanLanes : 0]);
+        turn ^= 1u;
+        return (int64_t)m;
+    };
+    tok_scan_walk<kCycle>(head, round, cycle, len, J.from, runs, J.cap, tid == 0, outs + job, (int64_t*)nullptr);
 }
 
 hipError_t launch_token_scan_batch(const TokScanJob* jobs, const int32_t* live, uint32_t nlive, TokScanOut* outs,
-                                   hipStream_t s) {
+                                   int32_t cycle, hipStream_t s) {
     if (nlive == 0) return hipSuccess;
-    hipLaunchKernelGGL(token_scan_batch_kernel<kScanBatchWaves>, dim3(nlive), dim3(kScanLanes * kScanBatchWaves), 0, s,
-                       jobs, live, outs);
+    const dim3 g(nlive), b(kScanLanes * kScanBatchWaves);
+    if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<kScanBatchWaves, true>), g, b, 0, s, jobs, live, outs);
+    else hipLaunchKernelGGL((token_scan_batch_kernel<kScanBatchWaves, false>), g, b, 0, s, jobs, live, outs);
     return hipGetLastError();
 }
 #ifdef RSH_KBENCH
 hipError_t launch_token_scan_batch_variant(uint32_t waves, const TokScanJob* jobs, const int32_t* live, uint32_t nlive,
-                                           TokScanOut* outs, hipStream_t s) {
+                                           TokScanOut* outs, int32_t cycle, hipStream_t s) {
     const dim3 g(nlive), b(kScanLanes * waves);
     switch (waves) {
-        case 1: hipLaunchKernelGGL(token_scan_batch_kernel<1>, g, b, 0, s, jobs, live, outs); break;
-        case 4: hipLaunchKernelGGL(token_scan_batch_kernel<4>, g, b, 0, s, jobs, live, outs); break;
-        case 8: hipLaunchKernelGGL(token_scan_batch_kernel<8>, g, b, 0, s, jobs, live, outs); break;
-        case 16: hipLaunchKernelGGL(token_scan_batch_kernel<16>, g, b, 0, s, jobs, live, outs); break;
+        case 1:
+            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<1, true>), g, b, 0, s, jobs, live, outs);
+            else hipLaunchKernelGGL((token_scan_batch_kernel<1, false>), g, b, 0, s, jobs, live, outs);
+            break;
+        case 4:
+            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<4, true>), g, b, 0, s, jobs, live, outs);
+            else hipLaunchKernelGGL((token_scan_batch_kernel<4, false>), g, b, 0, s, jobs, live, outs);
+            break;
+        case 8:
+            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<8, true>), g, b, 0, s, jobs, live, outs);
+            else hipLaunchKernelGGL((token_scan_batch_kernel<8, false>), g, b, 0, s, jobs, live, outs);
+            break;
+        case 16:
+            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<16, true>), g, b, 0, s, jobs, live, outs);
+            else hipLaunchKernelGGL((token_scan_batch_kernel<16, false>), g, b, 0, s, jobs, live, outs);
+            break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -58,6 +58,10 @@ enum Opt : int {
                            // 1 file_md5_kernel on the second stream, 2 split between the two by md5_plan (md5_file.h)
     OPT_MD5_LANE_KBPS,     // md5_plan: what one lane of file_md5_kernel digests, in 1000 bytes per second
     OPT_MD5_LINK_KBPS,     // ... and what the host path takes in (PCIe and the host's multi-buffer MD5), the same unit
+    OPT_TOKENS_CYCLE,      // resident Receivers' token walk: 1 = streams that repeat a short cycle of runs are proven whole
+                           // cycles per lane and round (token_scan.h); 0, the default = one run per round, the kernels
+                           // without the cycle round (with it a plain round of a long run measured 6 % slower:
+                           // DESIGN.md section 4, "Cycle rounds")
     OPT_COUNT
 };
 
@@ -78,6 +82,7 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"k1_prio", 1},             {"tokens_runs_batch", 4096}, {"resident_md5_bytes", 1LL << 30},
     {"scan_phase_map", 0},      {"k1_anyb", 1},         {"md5_device_slice", 64LL << 20},
     {"resident_md5", 0},        {"md5_lane_kbps", 52000}, {"md5_link_kbps", 27700000},
+    {"tokens_cycle", 0},
 };
 // MD5_SLICE_NOTE.  Measured with tools/md5_device_bench.py (profiles/md5_device/; DESIGN.md section 4, "Whole-file MD5s
 // on the device").  md5_lane_kbps: a lane of file_md5_kernel digests 75 MB/s with up to 8192 files on the chip and

@@ -547,9 +547,10 @@ int64_t untok_span_bytes(int64_t forced = 0) {
 
 // The walk over host pointers: the kernels' lanes one after another, `lanes` of them to a round (64: token_scan_kernel;
 // 64 W: token_scan_batch_kernel's W waves, each wave's pair found as the kernel's ballot finds it and the pairs added
-// up by the kernel's tok_scan_combine).
+// up by the kernel's tok_scan_combine).  A cycle round likewise: lane k's check of cycle k, each wave's leading lanes
+// that succeeded, the waves' counts combined, and the records stored lane by lane.
 void scan_host(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
-               uint32_t lanes = kScanLanes) {
+               uint32_t lanes = kScanLanes, bool try_cycle = opt(OPT_TOKENS_CYCLE) != 0, int64_t* cycles = nullptr) {
     auto ld = [&](int64_t off) { return get_int(tokens + off); };
     const uint32_t waves = lanes / kScanLanes;
     auto round = [&](int64_t pos, int32_t v) -> int64_t {
@@ -569,7 +570,26 @@ void scan_host(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, i
         }
         return tok_scan_combine(full, part, waves, per);
     };
-    tok_scan_walk(ld, round, len, from, runs, cap, true, out);
+    std::vector<TokCycleLane> cl(lanes);
+    auto cycle = [&](const TokCycle& T, int64_t pos, int64_t n, int32_t* x0) -> int64_t {
+        uint32_t full[kScanMaxWaves], part[kScanMaxWaves];
+        for (uint32_t w = 0; w < waves; ++w) {
+            full[w] = kScanLanes;
+            part[w] = 0;
+            for (uint32_t i = 0; i < kScanLanes; ++i) cl[kScanLanes * w + i] = tok_cycle_lane(ld, T, pos, len, kScanLanes * w + i);
+            for (uint32_t i = 0; i < kScanLanes; ++i)
+                if (!cl[kScanLanes * w + i].ok) {
+                    full[w] = i;
+                    break;
+                }
+        }
+        const int64_t m = tok_scan_combine(full, part, waves, 1u);
+        for (int64_t k = 0; k < m; ++k) tok_cycle_store(T, cl[(size_t)k], pos, (uint32_t)k, runs + n, k + 1 == m);
+        *x0 = m > 0 ? cl[(size_t)m - 1].last : 0;
+        return m;
+    };
+    if (try_cycle) tok_scan_walk<true>(ld, round, cycle, len, from, runs, cap, true, out, cycles);
+    else tok_scan_walk<false>(ld, round, cycle, len, from, runs, cap, true, out, cycles);
 }
 
 // token_unframe_kernel's work on one span, over host pointers: the same workgroup split, the same bytes one by one
@@ -613,18 +633,20 @@ void run_unspan_host(const UntokSpan& whole, const uint8_t** lo, const uint8_t**
 
 // One launch of the walk into c->tok_runs, its TokScanOut and records copied to c->h_runs: two small downloads.
 int scan_device_runs(rsh_ctx* c, const uint8_t* d_tokens, int64_t len, int64_t from, int64_t cap, TokScanOut* out,
-                     const TokRun** runs) {
-    constexpr size_t kHead = 32;  // the TokScanOut, then the records
-    static_assert(sizeof(TokScanOut) <= kHead, "TokScanOut");
+                     const TokRun** runs, int64_t* cycles = nullptr) {
+    constexpr size_t kHead = 32;  // the TokScanOut and the cycles that cycle rounds proved, then the records
+    static_assert(sizeof(TokScanOut) + sizeof(int64_t) == kHead, "TokScanOut");
     RSH_HIP(c->tok_runs.ensure(kHead + (size_t)cap * sizeof(TokRun)));
     RSH_HIP(c->h_runs.ensure(kHead + (size_t)cap * sizeof(TokRun)));
     uint8_t* d = c->tok_runs.as<uint8_t>();
     uint8_t* hp = c->h_runs.as<uint8_t>();
     RSH_HIP(launch_token_scan(d_tokens, len, from, reinterpret_cast<TokRun*>(d + kHead), cap,
-                              reinterpret_cast<TokScanOut*>(d), c->stream));
+                              reinterpret_cast<TokScanOut*>(d), opt(OPT_TOKENS_CYCLE) != 0,
+                              reinterpret_cast<int64_t*>(d + sizeof(TokScanOut)), c->stream));
     RSH_HIP(hipMemcpyAsync(hp, d, kHead, hipMemcpyDeviceToHost, c->stream));
     RSH_HIP(hipStreamSynchronize(c->stream));
     memcpy(out, hp, sizeof(TokScanOut));
+    if (cycles) memcpy(cycles, hp + sizeof(TokScanOut), sizeof(int64_t));
     if (out->n < 0 || out->n > cap) return RSH_E_DEVICE;
     if (out->n > 0) {
         RSH_HIP(hipMemcpyAsync(hp + kHead, d + kHead, (size_t)out->n * sizeof(TokRun), hipMemcpyDeviceToHost, c->stream));
@@ -712,7 +734,7 @@ int walk_round(rsh_ctx* c, const WalkBlock& W, size_t n, uint32_t nlive, bool fi
     RSH_HIP(c->tokb_outs.ensure(n * sizeof(TokScanOut)));
     TokScanOut* d_outs = c->tokb_outs.as<TokScanOut>();
     if (fill) RSH_HIP(hipMemsetAsync(d_outs, 0xFF, n * sizeof(TokScanOut), c->stream));
-    RSH_HIP(launch_token_scan_batch(W.jobs, W.live, nlive, d_outs, c->stream));
+    RSH_HIP(launch_token_scan_batch(W.jobs, W.live, nlive, d_outs, opt(OPT_TOKENS_CYCLE) != 0, c->stream));
     RSH_HIP(hipMemcpyAsync(W.outs, d_outs, n * sizeof(TokScanOut), hipMemcpyDeviceToHost, c->stream));
     RSH_HIP(hipStreamSynchronize(c->stream));
     return RSH_OK;
@@ -1060,31 +1082,43 @@ int rsh_debug_tokens_scan_batch_selftest(rsh_ctx* ctx, rsh_token_scan_job* jobs,
         jobs[i].n_runs = outs[(size_t)i].n;
         jobs[i].pos = outs[(size_t)i].pos;
         jobs[i].status = outs[(size_t)i].status;
+        jobs[i].reserved = outs[(size_t)i].rounds;
     }
     return RSH_OK;
 }
 
-int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
-                                   rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status) {
+int rsh_debug_tokens_scan_rounds_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
+                                          rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status,
+                                          int64_t* rounds, int64_t* cycles) {
     static_assert(sizeof(rsh_token_run) == sizeof(TokRun), "rsh_token_run is TokRun");
     if (!tokens || tokens_len < 0 || from < 0 || from > tokens_len || cap < 1 || cap > (1 << 24) || !runs || !n_runs ||
         !pos || !status)
         return RSH_E_INVAL;
     TokScanOut so;
+    int64_t proven = 0;
     if (ctx) {
         RSH_CLAIM(ctx);
         RSH_HIP(hipSetDevice(ctx->device));
         const TokRun* got = nullptr;
-        const int rc = scan_device_runs(ctx, tokens, tokens_len, from, cap, &so, &got);
+        const int rc = scan_device_runs(ctx, tokens, tokens_len, from, cap, &so, &got, &proven);
         if (rc != RSH_OK) return rc;
         memcpy(runs, got, (size_t)so.n * sizeof(TokRun));
     } else {
-        scan_host(tokens, tokens_len, from, reinterpret_cast<TokRun*>(runs), cap, &so);
+        scan_host(tokens, tokens_len, from, reinterpret_cast<TokRun*>(runs), cap, &so, kScanLanes,
+                  opt(OPT_TOKENS_CYCLE) != 0, &proven);
     }
     *n_runs = so.n;
     *pos = so.pos;
     *status = so.status;
+    if (rounds) *rounds = so.rounds;
+    if (cycles) *cycles = proven;
     return RSH_OK;
+}
+
+int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
+                                   rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status) {
+    return rsh_debug_tokens_scan_rounds_selftest(ctx, tokens, tokens_len, from, runs, cap, n_runs, pos, status, nullptr,
+                                                 nullptr);
 }
 
 int rsh_debug_untokens_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t pos, int32_t T,

@@ -40,7 +40,7 @@ struct TokScanOut {
     int64_t pos;     // END: the byte after putInt(0); MORE: the first token not listed; RSH_E_INVAL: the offending token
     int64_t n;       // records written
     int32_t status;
-    int32_t pad;
+    int32_t rounds;  // plain rounds plus cycle attempts of this pass
 };
 constexpr uint32_t kScanLanes = 64;
 // ints per lane of a match round (at 4, 2^20 consecutive match tokens took 2.78 ms to walk: kbench KBENCH_UNTOKENS,
@@ -71,16 +71,201 @@ RSH_HD uint32_t tok_scan_lane(const Load& ld, int64_t pos, int64_t len, int32_t 
     return c;
 }
 
+// ---- cycle rounds ----
+//
+// A stream whose runs are one token long (a match token and a literal token in turn: the half-modified file) gives the
+// plain round one token per round trip.  Where the records of a pass repeat a short cycle, every token start of the
+// following cycles is predictable: lane k takes cycle k, loads every header of it at the offsets the cycle's template
+// gives -- independent of each other and of the other lanes -- and the cycles proven are the leading lanes that
+// succeeded, as lane i of a literal round is proven by the lanes before it.  The rule:
+//   * attempted only at the start of a new record (a valid header that does not extend `last`), for R = 2, 3, 4 in
+//     turn, the first R such that the pass has 2 R records, the shapes (kind, literal length, count) of its last R equal
+//     those of the R before them, the R records have at most kCycleMaxTokens tokens, the header has the kind (and
+//     literal length) of record n - R, and the list has room for one cycle at least (lim = (cap - n) / R >= 1);
+//   * the template is records [n - R, n), the period P the distance from record n - R's header to pos;
+//   * lane k < lim takes part when its cycle [pos + k P, pos + (k + 1) P) is inside the stream; a literal record's ints
+//     all equal the template's length; a match record's first int x0 is negative and int t is x0 - t (negative too); a
+//     match record that follows a match token must not continue that token's index, so that records stay maximal (the
+//     token before a cycle's first record is the int 4 bytes before the cycle, which a lane after lane 0 reads: the
+//     lane before it proves that a header lies there);
+//   * the token after the last proven cycle is not trusted: the plain walk goes on from there and extends `last` when
+//     it continues it.  Errors and the end are found by the plain walk alone.
+// So the records, the end position and the status of every pass are the plain walk's at every capacity and width.
+// Literal data that looks like headers is harmless: a lane counts only when every lane before it succeeded.
+constexpr int32_t kCycleMaxTokens = 32;
+constexpr int kCycleMaxRecords = 4;    // R
+constexpr int kCycleHistory = 2 * kCycleMaxRecords;
+
+// A record's shape and place, as the walk remembers the last kCycleHistory records of the pass.
+struct TokShape {
+    int64_t pos;
+    int32_t h;  // LITERAL: the tokens' length; MATCH: -1
+    int32_t c;  // tokens, at most kCycleMaxTokens + 1 (more are no cycle's)
+};
+RSH_HD TokShape tok_shape(const TokRun& r) {
+    return TokShape{r.pos, r.kind == RSH_EV_LITERAL ? r.v : -1,
+                    (int32_t)(r.count > kCycleMaxTokens ? kCycleMaxTokens + 1 : r.count)};
+}
+
+struct TokCycle {
+    int32_t R;                        // records of the template
+    int32_t last_h;                   // h[R - 1]
+    int32_t h[kCycleMaxRecords];      // per record: the literal length, or -1
+    int32_t c[kCycleMaxRecords];      // ... its tokens
+    int64_t off[kCycleMaxRecords];    // ... its first header's offset in the cycle
+    int64_t P;                        // the cycle's bytes
+    int64_t lim;                      // cycles the list has room for
+};
+
+// S[0] is record n - 1, S[i] record n - 1 - i.  R is a compile-time value so that every index is.
+template <int R>
+RSH_HD bool tok_cycle_detect(const TokShape* S, int64_t n, int64_t cap, int64_t pos, int32_t v, TokCycle* T) {
+    if (n < 2 * R) return false;
+    int32_t tokens = 0;
+    bool same = true;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < R; ++i) {
+        same = same && S[i].h == S[i + R].h && S[i].c == S[i + R].c;
+        tokens += S[i].c;
+    }
+    if (!same || tokens > kCycleMaxTokens) return false;
+    if ((v > 0 ? v : -1) != S[R - 1].h) return false;
+    const int64_t lim = (cap - n) / R;
+    if (lim < 1) return false;
+    T->R = R;
+    T->last_h = S[0].h;
+    T->P = pos - S[R - 1].pos;
+    T->lim = lim;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < kCycleMaxRecords; ++j) {
+        const int i = j < R ? R - 1 - j : 0;
+        T->h[j] = S[i].h;
+        T->c[j] = j < R ? S[i].c : 0;
+        T->off[j] = S[i].pos - S[R - 1].pos;
+    }
+    return true;
+}
+
+// Lane k's cycle: whether every header of it is what the template says.  x0[j]: the first int of record j (a match
+// record's first index comes from it).  Every load lies in [pos + k P - 4, pos + (k + 1) P), inside the stream.
+struct TokCycleLane {
+    bool ok;
+    int32_t x0[kCycleMaxRecords];
+    int32_t last;  // x0[R - 1]
+};
+struct TokCycleCheck {
+    bool ok, after_match;
+    int32_t prev;  // the int of the match token before, when after_match
+    int32_t last;  // the first int of the latest record
+};
+// Record J of the cycle at q (J a compile-time value, so that a lane's values stay in registers): its first int.
+template <int J, class Load>
+RSH_HD int32_t tok_cycle_check(const Load& ld, const TokCycle& T, int64_t q, TokCycleCheck& s) {
+    if (J >= T.R) return 0;
+    const int64_t o = q + T.off[J];
+    const int32_t h = T.h[J], c = T.c[J];
+    const int32_t a = ld(o);
+    s.last = a;
+    if (h > 0) {
+        s.ok = s.ok && a == h;
+        for (int32_t t = 1; t < c; ++t) s.ok = (ld(o + (int64_t)t * ((int64_t)h + 4)) == h) && s.ok;
+        s.after_match = false;
+    } else {
+        s.ok = s.ok && a < 0 && !(s.after_match && a == (int32_t)((uint32_t)s.prev - 1u));
+        for (int32_t t = 1; t < c; ++t) {
+            const int32_t x = ld(o + 4 * (int64_t)t);
+            s.ok = (x < 0 && x == (int32_t)((uint32_t)a - (uint32_t)t)) && s.ok;
+        }
+        s.prev = (int32_t)((uint32_t)a - (uint32_t)(c - 1));
+        s.after_match = true;
+    }
+    return a;
+}
+template <class Load>
+RSH_HD TokCycleLane tok_cycle_lane(const Load& ld, const TokCycle& T, int64_t pos, int64_t len, uint32_t k) {
+    TokCycleLane r = {false, {0, 0, 0, 0}, 0};
+    if ((int64_t)k >= T.lim) return r;
+    const int64_t q = pos + (int64_t)k * T.P;
+    if (q + T.P > len) return r;
+    TokCycleCheck s = {true, false, 0, 0};
+    if (k > 0 && T.last_h < 0 && T.h[0] < 0) {
+        s.prev = ld(q - 4);
+        s.after_match = true;
+    }
+    static_assert(kCycleMaxRecords == 4, "one call per record");
+    r.x0[0] = tok_cycle_check<0>(ld, T, q, s);
+    r.x0[1] = tok_cycle_check<1>(ld, T, q, s);
+    r.x0[2] = tok_cycle_check<2>(ld, T, q, s);
+    r.x0[3] = tok_cycle_check<3>(ld, T, q, s);
+    r.ok = s.ok;
+    r.last = s.last;
+    return r;
+}
+
+// Record j of lane k's proven cycle.
+RSH_HD TokRun tok_cycle_record(const TokCycle& T, int64_t pos, int64_t k, int j, int32_t x0) {
+    const int32_t h = T.h[j];
+    return TokRun{pos + k * T.P + T.off[j], h > 0 ? RSH_EV_LITERAL : RSH_EV_MATCH, h > 0 ? h : ~x0, (int64_t)T.c[j]};
+}
+// Lane k stores its records at dst = runs + n, but for the very last record of the round (`tail`: this is the last
+// proven cycle), which the walk's writer stores as `last`: only that lane ever rewrites it.
+RSH_HD void tok_cycle_store(const TokCycle& T, const TokCycleLane& L, int64_t pos, uint32_t k, TokRun* dst, bool tail) {
+    TokRun* const d = dst + (int64_t)k * T.R;
+    const int keep = T.R - (tail ? 1 : 0);
+    if (0 < keep) d[0] = tok_cycle_record(T, pos, k, 0, L.x0[0]);
+    if (1 < keep) d[1] = tok_cycle_record(T, pos, k, 1, L.x0[1]);
+    if (2 < keep) d[2] = tok_cycle_record(T, pos, k, 2, L.x0[2]);
+    if (3 < keep) d[3] = tok_cycle_record(T, pos, k, 3, L.x0[3]);
+}
+
+// The history after a new record: S[0] becomes s.
+RSH_HD void tok_shape_push(TokShape* S, const TokShape& s) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = kCycleHistory - 1; i > 0; --i) S[i] = S[i - 1];
+    S[0] = s;
+}
+// ... after m proven cycles of R records: enough of them pushed to fill the history, the rest as a shift of P each.
+template <int R>
+RSH_HD void tok_shape_cycles(TokShape* S, int64_t P, int64_t m) {
+    constexpr int64_t kFill = (kCycleHistory + R - 1) / R;
+    const int64_t pushed = m < kFill ? m : kFill;
+    for (int64_t c = 0; c < pushed; ++c)
+        for (int j = 0; j < R; ++j) {
+            TokShape s = S[R - 1];  // the record one cycle before
+            s.pos += P;
+            tok_shape_push(S, s);
+        }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < kCycleHistory; ++i) S[i].pos += (m - pushed) * P;
+}
+
 // The walk from stream offset `from`: at most cap records.  head(pos): the int at pos, the same value in every lane;
 // round(pos, v): the tokens of the run that starts at pos proven in one round (>= 1: the caller of round has checked
 // the first token), the same value in every lane -- the host stand-in loops over the lanes, the kernel ballots.
-// writer: this lane stores the records and *out.
-template <class Head, class Round>
-RSH_HD void tok_scan_walk(const Head& head, const Round& round, int64_t len, int64_t from, TokRun* runs, int64_t cap,
-                          bool writer, TokScanOut* out) {
-    int64_t pos = from, n = 0;
-    int32_t status;
+// cycle(T, pos, n, &x0): a cycle round (above) from pos with n records listed: the cycles proven, the same value in
+// every lane; the lanes have stored their records at runs + n on (all but the last one) and x0 is the first int of the
+// last one; attempted when kCycle (option tokens_cycle picks the instantiation: with kCycle false the walk is the plain
+// walk's code and nothing else).  writer: this lane stores the records and *out (rounds: the
+// plain rounds plus the cycle attempts), and *cycles, the cycles that cycle rounds proved, when it is not null.
+template <bool kCycle, class Head, class Round, class Cycle>
+RSH_HD void tok_scan_walk(const Head& head, const Round& round, const Cycle& cycle, int64_t len,
+                          int64_t from, TokRun* runs, int64_t cap, bool writer, TokScanOut* out, int64_t* cycles) {
+    int64_t pos = from, n = 0, proven = 0;
+    int32_t status, rounds = 0;
     TokRun last = {0, 0, 0, 0};
+    TokShape S[kCycleHistory];  // S[i]: record n - 1 - i of this pass (S[0] is `last`, whose count may still grow)
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < kCycleHistory; ++i) S[i] = TokShape{0, 0, 0};
     for (;;) {
         if (pos + 4 > len) {  // the stream ended without putInt(0)
             status = RSH_E_INVAL;
@@ -102,17 +287,44 @@ RSH_HD void tok_scan_walk(const Head& head, const Round& round, int64_t len, int
             status = TOK_SCAN_MORE;
             break;
         }
+        if (kCycle && !ext && n >= 2 * 2) {  // `last` is complete: a new record starts here
+            S[0] = tok_shape(last);
+            TokCycle T;
+            if (tok_cycle_detect<2>(S, n, cap, pos, v, &T) || tok_cycle_detect<3>(S, n, cap, pos, v, &T) ||
+                tok_cycle_detect<4>(S, n, cap, pos, v, &T)) {
+                ++rounds;
+                int32_t x0 = 0;
+                const int64_t m = cycle(T, pos, n, &x0);
+                if (m > 0) {
+                    if (T.R == 2) tok_shape_cycles<2>(S, T.P, m);
+                    else if (T.R == 3) tok_shape_cycles<3>(S, T.P, m);
+                    else tok_shape_cycles<4>(S, T.P, m);
+                    last = TokRun{S[0].pos, T.last_h > 0 ? RSH_EV_LITERAL : RSH_EV_MATCH, T.last_h > 0 ? T.last_h : ~x0,
+                                  (int64_t)S[0].c};
+                    n += m * T.R;
+                    proven += m;
+                    if (writer) runs[n - 1] = last;
+                    pos += m * T.P;
+                    continue;  // (the token there is read as any other: it may extend `last`)
+                }
+            }
+        }
+        ++rounds;
         const int64_t m = round(pos, v);
         if (ext) {
             last.count += m;
         } else {
             last = TokRun{pos, kind, val, m};
             ++n;
+            if (kCycle) tok_shape_push(S, tok_shape(last));  // (its count is read again when the record is complete)
         }
         if (writer) runs[n - 1] = last;
         pos += v > 0 ? m * ((int64_t)v + 4) : 4 * m;
     }
-    if (writer) *out = TokScanOut{pos, n, status, 0};
+    if (writer) {
+        *out = TokScanOut{pos, n, status, rounds};
+        if (cycles) *cycles = proven;
+    }
 }
 
 // ---- the segment's walk ----

@@ -240,7 +240,8 @@ DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_rese
                  "rsh_debug_tokens_scan_batch_selftest", "rsh_debug_phase_plan", "rsh_debug_phase_map_selftest",
                  "rsh_debug_phase_round_b", "rsh_debug_phase_segments", "rsh_debug_k1_plan",
                  "rsh_debug_k1_plan_batch", "rsh_debug_md5_device_selftest", "rsh_debug_md5_closing",
-                 "rsh_debug_md5_plan", "rsh_debug_io_selftest", "rsh_debug_window_weak_selftest"]
+                 "rsh_debug_md5_plan", "rsh_debug_io_selftest", "rsh_debug_window_weak_selftest",
+                 "rsh_debug_tokens_scan_rounds_selftest"]
 
 _LIB = None
 
@@ -367,6 +368,9 @@ def lib():
                                           ctypes.c_int),
         "rsh_debug_tokens_scan_selftest": ([P, P, I64, I64, ctypes.POINTER(TokenRun), I64, ctypes.POINTER(I64),
                                             ctypes.POINTER(I64), ctypes.POINTER(I32)], ctypes.c_int),
+        "rsh_debug_tokens_scan_rounds_selftest": ([P, P, I64, I64, ctypes.POINTER(TokenRun), I64, ctypes.POINTER(I64),
+                                                   ctypes.POINTER(I64), ctypes.POINTER(I32), ctypes.POINTER(I64),
+                                                   ctypes.POINTER(I64)], ctypes.c_int),
         "rsh_debug_untokens_selftest": ([P, P, I64, I64, I32, I64, P, I64, ctypes.POINTER(I64), ctypes.POINTER(I64),
                                          ctypes.POINTER(I64)], ctypes.c_int),
         "rsh_tokens_frame_batch_device": ([P, ctypes.POINTER(TokenFrameJob), I32], ctypes.c_int),
@@ -553,13 +557,27 @@ def tokens_scan_selftest(tokens, length, start=0, cap=1 << 16, ctx=None):
     return [(r.pos, r.kind, r.value, r.count) for r in runs[:n.value]], pos.value, st.value
 
 
-def tokens_scan_batch_selftest(jobs, live=None, lanes=0, ctx=None):
+def tokens_scan_rounds_selftest(tokens, length, start=0, cap=1 << 16, ctx=None):
+    """rsh_debug_tokens_scan_rounds_selftest: tokens_scan_selftest's pass and what it took: (records, end position,
+    status, rounds, cycles) -- the walk's memory round trips (plain rounds plus cycle attempts, option tokens_cycle) and
+    the cycles that cycle rounds proved."""
+    runs = (TokenRun * cap)()
+    n, pos, st = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+    rounds, cycles = ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().rsh_debug_tokens_scan_rounds_selftest(None if ctx is None else ctx.handle, _addr(tokens), length, start,
+                                                       runs, cap, ctypes.byref(n), ctypes.byref(pos), ctypes.byref(st),
+                                                       ctypes.byref(rounds), ctypes.byref(cycles)))
+    return [(r.pos, r.kind, r.value, r.count) for r in runs[:n.value]], pos.value, st.value, rounds.value, cycles.value
+
+
+def tokens_scan_batch_selftest(jobs, live=None, lanes=0, ctx=None, rounds=False):
     """rsh_debug_tokens_scan_batch_selftest: one pass of the segment's token walk over the files `live` (indices into
     jobs; None: all).  jobs = [(tokens, length, start, cap[, runs])].  ctx None: tokens are uint8 arrays walked by the
     host stand-in with a round of `lanes` lanes (0: the kernel's width), and the result is [(records or None, end
     position, status)] per job, None and -1, -1 for a file that did not walk.  With a Context: tokens and runs are
     DeviceBuffers or device addresses (runs: room for cap records of 24 bytes), token_scan_batch_kernel walks all the
-    files in one launch, and the result is [(record count, end position, status)]; the records stay on the device."""
+    files in one launch, and the result is [(record count, end position, status)]; the records stay on the device.
+    rounds=True: each file's tuple ends with the rounds its pass took (-1 for a file that did not walk)."""
     n = len(jobs)
     tj = (TokenScanJob * max(n, 1))()
     keep = []
@@ -575,10 +593,11 @@ def tokens_scan_batch_selftest(jobs, live=None, lanes=0, ctx=None):
     order = np.ascontiguousarray(range(n) if live is None else live, dtype=np.int32)
     _check(lib().rsh_debug_tokens_scan_batch_selftest(None if ctx is None else ctx.handle, tj, n,
                                                       _ptr(order) if order.size else None, order.size, lanes))
+    more = (lambda i: (tj[i].reserved,)) if rounds else (lambda i: ())
     if ctx is not None:
-        return [(tj[i].n_runs, tj[i].pos, tj[i].status) for i in range(n)]
+        return [(tj[i].n_runs, tj[i].pos, tj[i].status) + more(i) for i in range(n)]
     return [([(r.pos, r.kind, r.value, r.count) for r in keep[i][:tj[i].n_runs]] if tj[i].n_runs >= 0 else None,
-             tj[i].pos, tj[i].status) for i in range(n)]
+             tj[i].pos, tj[i].status) + more(i) for i in range(n)]
 
 
 def untokens_selftest(tokens, length, pos, T, count, out, span=0, ctx=None):

@@ -184,7 +184,7 @@ static int tokens_main(int argc, char** argv) {
 //     rsh_receiver_combine_batch_resident's rounds (one launch for all files at 4096 records each, one download of the
 //     TokScanOuts, one copy launch of the records) against rsh_receiver_combine_resident's per file (a launch at 65536
 //     records and two small downloads each), wall time.
-static bool segment_walk(int nfiles, int reps, hipStream_t s) {
+static bool segment_walk(int nfiles, int reps, int32_t cyc, hipStream_t s) {
     const int64_t blocks = 16384, T = 8192;
     std::vector<uint8_t> ident((size_t)(4 * blocks + 4), 0), half;
     auto put = [](std::vector<uint8_t>& v, size_t at, int32_t x) { memcpy(v.data() + at, &x, 4); };
@@ -241,7 +241,7 @@ static bool segment_walk(int nfiles, int reps, hipStream_t s) {
                 rounds = 0;
                 while (!cur.empty()) {
                     memcpy(live, cur.data(), cur.size() * sizeof(int32_t));
-                    CK(rsh::launch_token_scan_batch(jobs, live, (uint32_t)cur.size(), d_outs, s));
+                    CK(rsh::launch_token_scan_batch(jobs, live, (uint32_t)cur.size(), d_outs, cyc, s));
                     CK(hipMemcpyAsync(h_outs, d_outs, (size_t)nfiles * sizeof(rsh::TokScanOut), hipMemcpyDeviceToHost, s));
                     CK(hipStreamSynchronize(s));
                     uint32_t ne = 0;
@@ -272,7 +272,7 @@ static bool segment_walk(int nfiles, int reps, hipStream_t s) {
                     int64_t from = 0;
                     do {
                         CK(rsh::launch_token_scan(d_st[(size_t)f], lens[(size_t)f], from, reinterpret_cast<rsh::TokRun*>(d_runs1),
-                                                  cap1, d_out1, s));
+                                                  cap1, d_out1, cyc, nullptr, s));
                         CK(hipMemcpyAsync(h_out1, d_out1, sizeof(rsh::TokScanOut), hipMemcpyDeviceToHost, s));
                         CK(hipStreamSynchronize(s));
                         if (h_out1->n > 0) {
@@ -293,14 +293,69 @@ static bool segment_walk(int nfiles, int reps, hipStream_t s) {
         }
     }
     ok = ok && records[0] == records[1];
-    printf("segment walk files=%d records=%lld  batch (%lld rounds) avg %.3f ms best %.3f ms  single-file calls avg %.3f ms "
+    printf("segment walk tokens_cycle=%d files=%d records=%lld  batch (%lld rounds) avg %.3f ms best %.3f ms  single-file calls avg %.3f ms "
            "best %.3f ms  batch / single %.3f  %s\n",
-           nfiles, (long long)records[0], (long long)rounds, tot[0] / reps, best[0], tot[1] / reps, best[1], tot[0] / tot[1],
+           (int)cyc, nfiles, (long long)records[0], (long long)rounds, tot[0] / reps, best[0], tot[1] / reps, best[1], tot[0] / tot[1],
            ok ? "walk=ok" : "walk=MISMATCH");
     return ok;
 }
 
+// One half-modified 128 MiB file's stream (8192 cycles of a match token and an 8192-byte literal token) on
+// token_scan_kernel and on token_scan_batch_kernel, tokens_cycle 1 against 0 rep by rep: each rep's time is printed, so
+// that medians and spreads can be taken from the log.
+static bool half_walk(int reps, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    const int64_t cycles = 8192, T = 8192, len = cycles * (8 + T) + 4, cap = 64 << 10;
+    std::vector<uint8_t> half((size_t)len, 0x5A);
+    for (int64_t c = 0; c < cycles; ++c) {
+        const int32_t m = (int32_t)(-(2 * c + 1)), l = (int32_t)T;
+        memcpy(half.data() + c * (8 + T), &m, 4);
+        memcpy(half.data() + c * (8 + T) + 4, &l, 4);
+    }
+    memset(half.data() + len - 4, 0, 4);
+    uint8_t* st;
+    rsh::TokRun* d_runs;
+    rsh::TokScanOut *d_out, so[4];
+    rsh::TokScanJob* pj;
+    int32_t* plive;
+    CK(hipMalloc(&st, (size_t)len));
+    CK(hipMemcpy(st, half.data(), (size_t)len, hipMemcpyHostToDevice));
+    CK(hipMalloc(&d_runs, (size_t)cap * sizeof(rsh::TokRun)));
+    CK(hipMalloc(&d_out, sizeof(rsh::TokScanOut)));
+    CK(hipHostMalloc(&pj, sizeof(rsh::TokScanJob), hipHostMallocDefault));
+    CK(hipHostMalloc(&plive, sizeof(int32_t), hipHostMallocDefault));
+    plive[0] = 0;
+    *pj = rsh::TokScanJob{st, len, 0, d_runs, cap};
+    const char* name[4] = {"one wave tokens_cycle=1", "one wave tokens_cycle=0", "batch tokens_cycle=1", "batch tokens_cycle=0"};
+    std::vector<float> t[4];
+    bool ok = true;
+    for (int r = 0; r < reps + 1; ++r) {  // (the first round warms all four up)
+        for (int k = 0; k < 4; ++k) {
+            CK(hipStreamSynchronize(s));
+            CK(hipEventRecord(e0, s));
+            if (k < 2) CK(rsh::launch_token_scan(st, len, 0, d_runs, cap, d_out, k == 0, nullptr, s));
+            else CK(rsh::launch_token_scan_batch(pj, plive, 1, d_out, k == 2, s));
+            CK(hipEventRecord(e1, s));
+            CK(hipEventSynchronize(e1));
+            float ms;
+            CK(hipEventElapsedTime(&ms, e0, e1));
+            CK(hipMemcpy(&so[k], d_out, sizeof(so[k]), hipMemcpyDeviceToHost));
+            ok = ok && so[k].status == rsh::TOK_SCAN_END && so[k].pos == len && so[k].n == 2 * cycles;
+            if (r > 0) t[k].push_back(ms);
+        }
+    }
+    for (int k = 0; k < 4; ++k) {
+        std::vector<float> v = t[k];
+        std::sort(v.begin(), v.end());
+        printf("half-modified walk %-24s stream=%lld bytes rounds=%d  median %.3f ms min %.3f ms max %.3f ms  reps:", name[k],
+               (long long)len, so[k].rounds, v[v.size() / 2], v.front(), v.back());
+        for (float x : t[k]) printf(" %.3f", x);
+        printf("  %s\n", ok ? "walk=ok" : "walk=MISMATCH");
+    }
+    return ok;
+}
+
 static int untokens_main(int argc, char** argv) {
+    const int32_t kCyc = rsh::opt(rsh::OPT_TOKENS_CYCLE) != 0;  // the one-file streams run what the library would
     const int64_t count = ((int64_t)atoll(argv[1]) << 20) / rsh::kTokStride;  // whole tokens
     const int64_t n = count * rsh::kTokData, slen = count * rsh::kTokStride + 4;
     int64_t span = atoll(getenv("KBENCH_UNTOKENS"));
@@ -403,7 +458,7 @@ static int untokens_main(int argc, char** argv) {
             for (int k = 0; k < 3; ++k) {
                 CK(hipStreamSynchronize(s));
                 CK(hipEventRecord(e0, s));
-                if (k == 0) CK(rsh::launch_token_scan(st, len, 0, d_runs, 1024, d_out, s));
+                if (k == 0) CK(rsh::launch_token_scan(st, len, 0, d_runs, 1024, d_out, kCyc, nullptr, s));
                 else CK(hipMemcpyAsync(k == 1 ? pageable.data() : pinned, st, (size_t)len, hipMemcpyDeviceToHost, s));
                 CK(hipEventRecord(e1, s));
                 CK(hipEventSynchronize(e1));
@@ -445,8 +500,8 @@ static int untokens_main(int argc, char** argv) {
                 for (int k = 0; k < 2; ++k) {
                     CK(hipStreamSynchronize(s));
                     CK(hipEventRecord(e0, s));
-                    if (k == 0) CK(rsh::launch_token_scan(st, len, 0, d_runs, 1024, d_out, s));
-                    else CK(rsh::launch_token_scan_batch_variant(waves, pj, plive, 1, d_bout, s));
+                    if (k == 0) CK(rsh::launch_token_scan(st, len, 0, d_runs, 1024, d_out, kCyc, nullptr, s));
+                    else CK(rsh::launch_token_scan_batch_variant(waves, pj, plive, 1, d_bout, kCyc, s));
                     CK(hipEventRecord(e1, s));
                     CK(hipEventSynchronize(e1));
                     float ms;
@@ -469,7 +524,9 @@ static int untokens_main(int argc, char** argv) {
                    ok ? "walk=ok" : "walk=MISMATCH");
         }
     }
-    if (getenv("KBENCH_UNTOKENS_FILES")) walk_ok = segment_walk(atoi(getenv("KBENCH_UNTOKENS_FILES")), reps, s) && walk_ok;
+    walk_ok = half_walk(reps, s, e0, e1) && walk_ok;
+    if (getenv("KBENCH_UNTOKENS_FILES"))
+        for (int32_t cyc : {1, 0}) walk_ok = segment_walk(atoi(getenv("KBENCH_UNTOKENS_FILES")), reps, cyc, s) && walk_ok;
     return same && walk_ok ? 0 : 1;
 }
 
