@@ -8,12 +8,17 @@
  * k1_unaligned, scan_trace, scan_segmented, scan_samples, batch_chain, batch_chain_prefix, host_cores,
  * file_tile, file_tile_above, probe_long, segment_bytes, md5_width, chain_helpers, chain_map_bytes, time_gen, batch_warm,
  * fault_inject, tokens_span, tokens_piece, sums_piece, tokens_runs, k1_dma, k1_prio, tokens_runs_batch, resident_md5_bytes,
- * scan_phase_map, k1_anyb, md5_device_slice, resident_md5, md5_lane_kbps, md5_link_kbps, tokens_cycle.
+ * scan_phase_map, k1_anyb, md5_device_slice, resident_md5, md5_lane_kbps, md5_link_kbps, tokens_cycle, tokens_wide.
  *
  * tokens_cycle = 1: the resident Receivers' token walk (token_scan_kernel, token_scan_batch_kernel) proves whole cycles
  * of runs per lane where a pass's records repeat a cycle of 2 to 4 records (the half-modified file's match token and
  * literal token in turn); 0 (default): one run per round, the kernels' instantiation without the cycle round.  The
  * records, positions and statuses are identical in both.
+ *
+ * tokens_wide = K > 0: a pass of the walk yields (status 2) after K rounds in a row that each proved the round's full
+ * width, and token_run_kernel finds the end of that run with a whole grid in one launch; the resident Receivers add the
+ * tokens it proved to the yielded record and resume behind them.  0 (default): never, the kernels' instantiation
+ * without the yield.  The records, results, statuses and target bytes are identical at every K.
  *
  * resident_md5 = 0 (default): the segment Receiver's verify digests come down to the host; 1: file_md5_kernel digests
  * every finished file where it lies, on the context's second stream; 2: the files up to the planner's length cut on the
@@ -157,11 +162,39 @@ typedef struct {
 } rsh_token_run;
 int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
                                    rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status);
+/* (Under tokens_wide > 0 a pass of this and the next two entries may end with status 2, TOK_SCAN_LONG: pos is then the
+ * next token start and the last record the run so far.) */
 /* The same pass, and what it took: *rounds the memory round trips of the walk (plain rounds plus cycle attempts, option
  * tokens_cycle), *cycles the cycles that cycle rounds proved (either may be NULL). */
 int rsh_debug_tokens_scan_rounds_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t from,
                                           rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status,
                                           int64_t* rounds, int64_t* cycles);
+
+/* The run finder, token_run_kernel, alone: how many further tokens continue a run from the token start `pos`, where a
+ * continuing token holds v (a literal run: the tokens' length T; a match run: ~(first + count) of the record extended),
+ * examining at most `max` tokens (clamped to what the rest of the stream can hold, and to 2^31 for a match run): *m is
+ * the smallest failing token's index, or the clamped max.  ctx == NULL: host pointers and the host stand-in; otherwise
+ * device memory and the kernel.  groups == 0: the production choice of workgroups per job; otherwise that many
+ * (1 .. 1024), so that a workgroup's second and third chunk are reached on small streams. */
+int rsh_debug_tokens_run_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t pos, int32_t v,
+                                  int64_t max, int32_t groups, int64_t* m);
+/* The stream offsets [*lo, *hi) that this thread's last rsh_debug_tokens_run_selftest(NULL, ...) loaded (0, 0 when it
+ * loaded nothing). */
+int rsh_debug_tokens_run_extent(int64_t* lo, int64_t* hi);
+
+/* A whole walk to its end through the driver the resident Receivers use (every pass, finder launch and download under
+ * the options as they stand): all the records in stream order into runs[0, max_runs) (*n_runs counts them all;
+ * RSH_E_NOSPACE when there are more), *pos the byte after putInt(0) or the offending token, *status 1 or RSH_E_INVAL.
+ * `cap`: records per pass.  ctx == NULL: host memory and the stand-ins with rounds `lanes` lanes wide (a multiple of 64
+ * up to 1024; 0: 64).  Otherwise device memory: lanes 64 (or 0) is rsh_receiver_combine_resident's walk
+ * (token_scan_kernel), lanes 256 rsh_receiver_combine_batch_resident's on one file (token_scan_batch_kernel).
+ * stats (may be NULL): passes, rounds, finder launches, tokens the finder proved. */
+int rsh_debug_tokens_walk_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t cap, int32_t lanes,
+                                   rsh_token_run* runs, int64_t max_runs, int64_t* n_runs, int64_t* pos, int32_t* status,
+                                   int64_t stats[4]);
+/* The same four numbers for the walk of the context's last resident call (rsh_receiver_combine_resident,
+ * rsh_receiver_combine_batch_resident: every file's passes and rounds added up) or device walk selftest. */
+int rsh_debug_walk_stats(rsh_ctx* ctx, int64_t stats[4]);
 
 /* The segment's walk, token_scan_batch_kernel: one pass over the files live[0, nlive) (distinct indices into jobs), each
  * from its own `from` into its own `runs` (cap records, 1 .. 2^24), a workgroup per file.  ctx == NULL: tokens and runs

@@ -210,7 +210,7 @@ int rsh_ctx_trim(rsh_ctx* ctx) {
                       &ctx->md5_lanes, &ctx->md5_out})
         b->release();
     for (PinnedBuf* b : {&ctx->h_stage, &ctx->h_rcv_ops[0], &ctx->h_rcv_ops[1], &ctx->h_out, &ctx->h_tok, &ctx->h_tokd[0],
-                         &ctx->h_tokd[1], &ctx->h_sums, &ctx->h_sumsd, &ctx->h_tokb, &ctx->h_tokb_runs, &ctx->h_rmd5,
+                         &ctx->h_tokd[1], &ctx->h_sums, &ctx->h_sumsd, &ctx->h_tokb, &ctx->h_tokb_runs, &ctx->h_rmd5, &ctx->h_long,
                          &ctx->h_md5_lanes, &ctx->h_md5_out})
         b->release();
     if (ctx->h_win.cap > (1u << 20)) ctx->h_win.release();  // (a Receiver pass's pieces; the scan's windows are small)

@@ -325,6 +325,10 @@ struct rsh_ctx {
     // segment's walk (with the outs' host copy), the records' host copy, and the staging of the verify digests' bytes
     DevBuf tokb_runs, tokb_outs;
     PinnedBuf h_tokb, h_tokb_runs, h_rmd5;
+    // ... option tokens_wide: the run finder's descriptors and the host copy of its result words (pinned), and what the
+    // last resident call's walk took: passes, rounds, finder launches, tokens the finder proved (rsh_debug_walk_stats)
+    PinnedBuf h_long;
+    int64_t walk_stats[4] = {0, 0, 0, 0};
     hipEvent_t ev_sums_a = nullptr, ev_sums_b = nullptr;  // timing: the last sums kernel (rsh_debug_kernel_ms)
     bool sums_timed = false;
     // rsh_file_md5_batch_device (md5_device.cpp): a launch's lanes and results in HBM, their pinned host sides, and the
@@ -346,7 +350,7 @@ struct rsh_ctx {
         for (PinnedBuf* b : {&h_weak, &h_strong, &h_aw, &h_as, &h_fl, &h_pw[0], &h_ps[0], &h_pw[1], &h_ps[1], &h_lead, &h_pos, &h_out, &h_iv,
                              &h_tiles, &h_keys, &h_first, &h_win, &h_ptiles, &h_psegs, &h_hit, &h_win0, &h_pend, &h_bucket, &h_files,
                              &h_stage, &h_rcv_ops[0], &h_rcv_ops[1], &h_prep, &h_stamps, &h_fgw, &h_fjobs, &h_fout,
-                             &h_tok, &h_tokd[0], &h_tokd[1], &h_sums, &h_sumsd, &h_runs, &h_untok, &h_tokb, &h_tokb_runs, &h_rmd5,
+                             &h_tok, &h_tokd[0], &h_tokd[1], &h_sums, &h_sumsd, &h_runs, &h_untok, &h_tokb, &h_tokb_runs, &h_rmd5, &h_long,
                              &h_pm, &h_pmw, &h_pms, &h_pm_segs, &h_md5_lanes, &h_md5_out})
             b->release();
         if (abort_word) (void)hipFree(abort_word);

@@ -375,14 +375,21 @@ struct TokRun;
 struct TokScanOut;
 struct UntokSpan;
 // cycle: option tokens_cycle (cycle rounds are attempted); cycles (device memory, or null): the cycles they proved.
+// wide: option tokens_wide (> 0: the pass yields on a long run and fills *lng, device memory).
+struct TokLong;
 hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
-                             int32_t cycle, int64_t* cycles, hipStream_t s);
+                             int32_t cycle, int64_t* cycles, hipStream_t s, int32_t wide = 0, TokLong* lng = nullptr);
 hipError_t launch_token_unframe(const UntokSpan* spans, uint32_t n, uint32_t max_len, hipStream_t s);
 // A segment's walk: one workgroup per entry of live[0, nlive), each an index into jobs (both in pinned host memory);
 // file j's TokScanOut goes to outs[j] (device memory), its records where its descriptor says.
 struct TokScanJob;
+// wide > 0: file j's TokLong goes to lngs[j] (device memory) when its pass yields.
 hipError_t launch_token_scan_batch(const TokScanJob* jobs, const int32_t* live, uint32_t nlive, TokScanOut* outs,
-                                   int32_t cycle, hipStream_t s);
+                                   int32_t cycle, hipStream_t s, int32_t wide = 0, TokLong* lngs = nullptr);
+// The run finder: grid (groups, njobs) over jobs (pinned host or device memory); job j's result is res[jobs[j].slot].m
+// (device memory), which holds all ones before the launch.  groups: 1 .. 1024 (tok_run_groups), njobs below 65536.
+struct TokRunJob;
+hipError_t launch_token_run(const TokRunJob* jobs, uint32_t njobs, uint32_t groups, TokLong* res, hipStream_t s);
 #ifdef RSH_KBENCH
 // (kbench: the round's width in waves, 1, 4, 8 or 16)
 hipError_t launch_token_scan_batch_variant(uint32_t waves, const TokScanJob* jobs, const int32_t* live, uint32_t nlive,

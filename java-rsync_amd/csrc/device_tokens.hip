@@ -5,7 +5,7 @@
 // run list, one wave proving up to 64 literal or 1024 match tokens per memory round trip, and the literal runs placed
 // from the raw stream, the framer's mirror on the framer's grid (token_scan.h; receiver.cpp plans and owns the entry
 // points).  token_scan_batch_kernel: the walk of a segment's files in one launch, a workgroup per file and several
-// waves to a round.
+// waves to a round.  token_run_kernel: the end of one long run found by a whole grid at once (option tokens_wide).
 #include <hip/hip_runtime.h>
 
 #include "device.h"
@@ -181,10 +181,12 @@ hipError_t launch_token_unframe(const UntokSpan* spans, uint32_t n, uint32_t max
 // wave-uniform values, lane 0 stores the records.  A cycle round (option tokens_cycle): lane k checks cycle k, the
 // ballot's leading lanes are the cycles proven, each of those lanes stores its own records, and the last one's first
 // int comes back by a lane read.
-template <bool kCycle>
+// kWide (option tokens_wide): after `wide` full rounds in a row the pass ends LONG and lane 0 fills *lng.
+template <bool kCycle, bool kWide>
 __global__ __launch_bounds__(kScanLanes) void token_scan_kernel(const uint8_t* __restrict__ tokens, int64_t len, int64_t from,
                                                                TokRun* __restrict__ runs, int64_t cap, TokScanOut* __restrict__ out,
-                                                               int64_t* __restrict__ cycles) {
+                                                               int64_t* __restrict__ cycles, int32_t wide,
+                                                               TokLong* __restrict__ lng) {
     typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
     const GlobalByte base = (GlobalByte)(uintptr_t)tokens;
     const uint32_t lane = threadIdx.x;
@@ -209,13 +211,20 @@ __global__ __launch_bounds__(kScanLanes) void token_scan_kernel(const uint8_t* _
         *x0 = __builtin_amdgcn_readfirstlane(__shfl(c.last, m > 0 ? (int)m - 1 : 0));
         return (int64_t)__builtin_amdgcn_readfirstlane((int)m);
     };
-    tok_scan_walk<kCycle>(head, round, cycle, len, from, runs, cap, lane == 0, out, cycles);
+    tok_scan_walk<kCycle, kWide>(head, round, cycle, len, from, runs, cap, lane == 0, out, cycles, wide, kScanLanes, lng);
 }
 
 hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
-                             int32_t cycle, int64_t* cycles, hipStream_t s) {
-    if (cycle) hipLaunchKernelGGL(token_scan_kernel<true>, dim3(1), dim3(kScanLanes), 0, s, tokens, len, from, runs, cap, out, cycles);
-    else hipLaunchKernelGGL(token_scan_kernel<false>, dim3(1), dim3(kScanLanes), 0, s, tokens, len, from, runs, cap, out, cycles);
+                             int32_t cycle, int64_t* cycles, hipStream_t s, int32_t wide, TokLong* lng) {
+    const dim3 g(1), b(kScanLanes);
+    if (wide > 0 && !lng) return hipErrorInvalidValue;
+    if (wide > 0) {
+        if (cycle) hipLaunchKernelGGL((token_scan_kernel<true, true>), g, b, 0, s, tokens, len, from, runs, cap, out, cycles, wide, lng);
+        else hipLaunchKernelGGL((token_scan_kernel<false, true>), g, b, 0, s, tokens, len, from, runs, cap, out, cycles, wide, lng);
+    } else {
+        if (cycle) hipLaunchKernelGGL((token_scan_kernel<true, false>), g, b, 0, s, tokens, len, from, runs, cap, out, cycles, wide, lng);
+        else hipLaunchKernelGGL((token_scan_kernel<false, false>), g, b, 0, s, tokens, len, from, runs, cap, out, cycles, wide, lng);
+    }
     return hipGetLastError();
 }
 
@@ -228,10 +237,12 @@ hipError_t launch_token_scan(const uint8_t* tokens, int64_t len, int64_t from, T
 // A cycle round (option tokens_cycle) is a round like the others -- one barrier, the other pair buffer -- with thread
 // 64 w + i on cycle 64 w + i: beside its pair a wave leaves the first int of the last record of its last leading lane,
 // which is the round's last proven cycle when the count ends in that wave.
-template <uint32_t W, bool kCycle>
+// kWide: as token_scan_kernel's, a full round being all W waves'; file j's TokLong is lngs[j].
+template <uint32_t W, bool kCycle, bool kWide>
 __global__ __launch_bounds__(kScanLanes * W) void token_scan_batch_kernel(const TokScanJob* __restrict__ jobs,
                                                                          const int32_t* __restrict__ live,
-                                                                         TokScanOut* __restrict__ outs) {
+                                                                         TokScanOut* __restrict__ outs, int32_t wide,
+                                                                         TokLong* __restrict__ lngs) {
     typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
     typedef TokRun __attribute__((address_space(1))) * GlobalRuns;
     __shared__ uint32_t s_full[2][W], s_part[2][W];
@@ -281,15 +292,22 @@ __global__ __launch_bounds__(kScanLanes * W) void token_scan_batch_kernel(const 
         turn ^= 1u;
         return (int64_t)m;
     };
-    tok_scan_walk<kCycle>(head, round, cycle, len, J.from, runs, J.cap, tid == 0, outs + job, (int64_t*)nullptr);
+    tok_scan_walk<kCycle, kWide>(head, round, cycle, len, J.from, runs, J.cap, tid == 0, outs + job, (int64_t*)nullptr, wide,
+                                 kScanLanes * W, kWide ? lngs + job : nullptr);
 }
 
 hipError_t launch_token_scan_batch(const TokScanJob* jobs, const int32_t* live, uint32_t nlive, TokScanOut* outs,
-                                   int32_t cycle, hipStream_t s) {
+                                   int32_t cycle, hipStream_t s, int32_t wide, TokLong* lngs) {
     if (nlive == 0) return hipSuccess;
+    if (wide > 0 && !lngs) return hipErrorInvalidValue;
     const dim3 g(nlive), b(kScanLanes * kScanBatchWaves);
-    if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<kScanBatchWaves, true>), g, b, 0, s, jobs, live, outs);
-    else hipLaunchKernelGGL((token_scan_batch_kernel<kScanBatchWaves, false>), g, b, 0, s, jobs, live, outs);
+    if (wide > 0) {
+        if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<kScanBatchWaves, true, true>), g, b, 0, s, jobs, live, outs, wide, lngs);
+        else hipLaunchKernelGGL((token_scan_batch_kernel<kScanBatchWaves, false, true>), g, b, 0, s, jobs, live, outs, wide, lngs);
+    } else {
+        if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<kScanBatchWaves, true, false>), g, b, 0, s, jobs, live, outs, wide, lngs);
+        else hipLaunchKernelGGL((token_scan_batch_kernel<kScanBatchWaves, false, false>), g, b, 0, s, jobs, live, outs, wide, lngs);
+    }
     return hipGetLastError();
 }
 #ifdef RSH_KBENCH
@@ -298,26 +316,91 @@ hipError_t launch_token_scan_batch_variant(uint32_t waves, const TokScanJob* job
     const dim3 g(nlive), b(kScanLanes * waves);
     switch (waves) {
         case 1:
-            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<1, true>), g, b, 0, s, jobs, live, outs);
-            else hipLaunchKernelGGL((token_scan_batch_kernel<1, false>), g, b, 0, s, jobs, live, outs);
+            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<1, true, false>), g, b, 0, s, jobs, live, outs, 0, (TokLong*)nullptr);
+            else hipLaunchKernelGGL((token_scan_batch_kernel<1, false, false>), g, b, 0, s, jobs, live, outs, 0, (TokLong*)nullptr);
             break;
         case 4:
-            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<4, true>), g, b, 0, s, jobs, live, outs);
-            else hipLaunchKernelGGL((token_scan_batch_kernel<4, false>), g, b, 0, s, jobs, live, outs);
+            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<4, true, false>), g, b, 0, s, jobs, live, outs, 0, (TokLong*)nullptr);
+            else hipLaunchKernelGGL((token_scan_batch_kernel<4, false, false>), g, b, 0, s, jobs, live, outs, 0, (TokLong*)nullptr);
             break;
         case 8:
-            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<8, true>), g, b, 0, s, jobs, live, outs);
-            else hipLaunchKernelGGL((token_scan_batch_kernel<8, false>), g, b, 0, s, jobs, live, outs);
+            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<8, true, false>), g, b, 0, s, jobs, live, outs, 0, (TokLong*)nullptr);
+            else hipLaunchKernelGGL((token_scan_batch_kernel<8, false, false>), g, b, 0, s, jobs, live, outs, 0, (TokLong*)nullptr);
             break;
         case 16:
-            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<16, true>), g, b, 0, s, jobs, live, outs);
-            else hipLaunchKernelGGL((token_scan_batch_kernel<16, false>), g, b, 0, s, jobs, live, outs);
+            if (cycle) hipLaunchKernelGGL((token_scan_batch_kernel<16, true, false>), g, b, 0, s, jobs, live, outs, 0, (TokLong*)nullptr);
+            else hipLaunchKernelGGL((token_scan_batch_kernel<16, false, false>), g, b, 0, s, jobs, live, outs, 0, (TokLong*)nullptr);
             break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 #endif
+
+// The run finder (token_scan.h, "wide rounds"): grid (groups, jobs).  Workgroup g of a job takes chunks g, g + G,
+// g + 2 G, ... in ascending order, kRunDepth of them to an iteration so that independent chunks' loads are in flight
+// together; thread t plays lane t of tok_scan_lane in each.  A thread's first failing token is the chunk's first token
+// + its lane's base + its leading count.  A wave that meets a failure reduces it over its lanes, takes the minimum
+// into the workgroup's LDS word and stops: every later chunk of it lies behind.  Before an iteration a wave reads the
+// job's result word and the LDS word and leaves when its first chunk starts at or behind either -- an optimisation
+// only: a stale value costs work, the minimum does not depend on order.  The workgroup ends with one 64-bit minimum
+// on the result word (which holds all ones before the launch).  Nothing waits on another workgroup.
+__global__ __launch_bounds__(kRunThreads) void token_run_kernel(const TokRunJob* __restrict__ jobs, TokLong* __restrict__ res) {
+    typedef const uint8_t __attribute__((address_space(1))) * GlobalByte;
+    __shared__ unsigned long long s_min;
+    const TokRunJob J = jobs[blockIdx.y];
+    const GlobalByte base = (GlobalByte)(uintptr_t)J.tokens;
+    unsigned long long* const word = &res[J.slot].m;
+    const uint32_t tid = threadIdx.x, G = gridDim.x;
+    const uint32_t per = J.v > 0 ? 1u : kScanMatchPer;
+    const int64_t C = tok_run_chunk_tokens(J.v), chunks = (J.max + C - 1) / C;
+    const unsigned long long none = ~0ull, most = (unsigned long long)J.max;
+    auto ld = [&](int64_t off) -> int32_t {
+        const GlobalByte p = base + off;
+        return (int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24));
+    };
+    if (tid == 0) s_min = most;
+    __syncthreads();
+    for (int64_t k0 = blockIdx.x; k0 < chunks; k0 += (int64_t)kRunDepth * G) {
+        const unsigned long long seen = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long mine = __hip_atomic_load(&s_min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const unsigned long long first = (unsigned long long)(k0 * C);
+        if (first >= seen || first >= mine) break;
+        uint32_t c[kRunDepth];
+#pragma unroll
+        for (uint32_t u = 0; u < kRunDepth; ++u) {
+            const int64_t k = k0 + (int64_t)u * G;
+            c[u] = k < chunks ? tok_run_lane(ld, J, k * C, tid) : per;
+        }
+        unsigned long long best = none;
+#pragma unroll
+        for (uint32_t u = kRunDepth; u-- > 0;) {  // (ascending chunks: the lowest one that fails is taken last)
+            const int64_t k = k0 + (int64_t)u * G;
+            if (c[u] < per) best = (unsigned long long)(k * C + (int64_t)per * tid + c[u]);
+        }
+        if (__any(best != none)) {
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) {
+                const unsigned long long o = __shfl_xor(best, d);
+                best = o < best ? o : best;
+            }
+            if (tid % kScanLanes == 0) atomicMin(&s_min, best);
+            break;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned long long m = s_min;
+        atomicMin(word, m < most ? m : most);
+    }
+}
+
+hipError_t launch_token_run(const TokRunJob* jobs, uint32_t njobs, uint32_t groups, TokLong* res, hipStream_t s) {
+    if (njobs == 0) return hipSuccess;
+    if (groups == 0 || groups > kRunMaxGroups || njobs > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(token_run_kernel, dim3(groups, njobs), dim3(kRunThreads), 0, s, jobs, res);
+    return hipGetLastError();
+}
 
 // This file's code object, loaded by rsh_ctx_create (as warm_io_kernel for device_io.hip).
 __global__ void warm_tokens_kernel() {}

@@ -62,6 +62,11 @@ enum Opt : int {
                            // cycles per lane and round (token_scan.h); 0, the default = one run per round, the kernels
                            // without the cycle round (with it a plain round of a long run measured 6 % slower:
                            // DESIGN.md section 4, "Cycle rounds")
+    OPT_TOKENS_WIDE,       // resident Receivers' token walk: K > 0 = a pass yields after K full rounds in a row and
+                           // token_run_kernel finds the end of that run grid-wide in one launch (token_scan.h, "wide
+                           // rounds"); 0, the default = never, the kernels without the yield (their listings are the
+                           // ones from before the option).  K comes from two measurements, K x t_round >= 2 x t_yield
+                           // (WIDE_NOTE below)
     OPT_COUNT
 };
 
@@ -82,13 +87,19 @@ inline constexpr OptInfo kOpts[OPT_COUNT] = {
     {"k1_prio", 1},             {"tokens_runs_batch", 4096}, {"resident_md5_bytes", 1LL << 30},
     {"scan_phase_map", 0},      {"k1_anyb", 1},         {"md5_device_slice", 64LL << 20},
     {"resident_md5", 0},        {"md5_lane_kbps", 52000}, {"md5_link_kbps", 27700000},
-    {"tokens_cycle", 0},
+    {"tokens_cycle", 0},        {"tokens_wide", 0},
 };
-// MD5_SLICE_NOTE.  Measured with tools/md5_device_bench.py (profiles/md5_device/; DESIGN.md section 4, "Whole-file MD5s
-// on the device").  md5_lane_kbps: a lane of file_md5_kernel digests 75 MB/s with up to 8192 files on the chip and
-// 52 MB/s with all 131072 lanes resident (two waves share a SIMD's VALU); the planner takes the lower.  md5_link_kbps:
-// the host path (download + md5_files on 16 cores) took in 27.7 GB/s at 8192 files of 1 MiB, its best shape (5.8 GB/s
-// at 64 KiB files).  The default slice of 64 MiB per file and launch is 0.9 s at 75 MB/s and 1.3 s at 52 MB/s.
+// WIDE_NOTE.  The default of tokens_wide follows a rule ("Wide rounds"): K is the smallest power
+// of two with K x t_round >= 2 x t_yield, and it ships only if the whole walk of 2^20 match tokens beats the stream's
+// pinned download, the 1 GiB literal stream beats the plain walk, and streams that never yield are not slowed;
+// otherwise 0 ships.  Measured on one MI355X (kbench KBENCH_UNTOKENS, profiles/untokens/kbench_walk_wide_*):
+// t_round = 1.30 us (the one-wave walk of 2^20 match tokens, 1.329-1.333 ms over 1024 rounds); t_yield = 42 us (the
+// whole walk of that stream is 60 us + K x 1.36 us: two passes and a finder launch, of which one pass, 18 us, is the
+// plain walk's own; the finder's launch and download alone are 25 us).  2 x 42 / 1.30 = 65, so K = 128 (64 x 1.30 us
+// falls 1 us short).  At K = 128 the 2^20-match walk takes 0.235 ms on one wave against 0.086 ms for the download,
+// and 0.148 ms at K = 64: the first bar is missed at the K the rule gives (it holds only at K = 8: 0.071 ms), so the
+// default is 0 (streams that never yield also walk 0.6 to 2 % slower with the yield compiled in).  The literal
+// stream's walk is 0.14 ms at K = 64 against 2.55 ms.
 
 inline const OptInfo* opt_info() { return kOpts; }
 

@@ -549,8 +549,11 @@ int64_t untok_span_bytes(int64_t forced = 0) {
 // 64 W: token_scan_batch_kernel's W waves, each wave's pair found as the kernel's ballot finds it and the pairs added
 // up by the kernel's tok_scan_combine).  A cycle round likewise: lane k's check of cycle k, each wave's leading lanes
 // that succeeded, the waves' counts combined, and the records stored lane by lane.
+// wide (option tokens_wide) > 0: the pass yields as the kernels' does, and *lng is filled.
+int32_t wide_opt() { return (int32_t)std::min<int64_t>(std::max<int64_t>(opt(OPT_TOKENS_WIDE), 0), INT32_MAX); }
 void scan_host(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, int64_t cap, TokScanOut* out,
-               uint32_t lanes = kScanLanes, bool try_cycle = opt(OPT_TOKENS_CYCLE) != 0, int64_t* cycles = nullptr) {
+               uint32_t lanes = kScanLanes, bool try_cycle = opt(OPT_TOKENS_CYCLE) != 0, int64_t* cycles = nullptr,
+               int32_t wide = wide_opt(), TokLong* lng = nullptr) {
     auto ld = [&](int64_t off) { return get_int(tokens + off); };
     const uint32_t waves = lanes / kScanLanes;
     auto round = [&](int64_t pos, int32_t v) -> int64_t {
@@ -588,8 +591,55 @@ void scan_host(const uint8_t* tokens, int64_t len, int64_t from, TokRun* runs, i
         *x0 = m > 0 ? cl[(size_t)m - 1].last : 0;
         return m;
     };
-    if (try_cycle) tok_scan_walk<true>(ld, round, cycle, len, from, runs, cap, true, out, cycles);
-    else tok_scan_walk<false>(ld, round, cycle, len, from, runs, cap, true, out, cycles);
+    TokLong unused;
+    if (!lng) lng = &unused;
+    if (wide > 0) {
+        if (try_cycle) tok_scan_walk<true, true>(ld, round, cycle, len, from, runs, cap, true, out, cycles, wide, lanes, lng);
+        else tok_scan_walk<false, true>(ld, round, cycle, len, from, runs, cap, true, out, cycles, wide, lanes, lng);
+    } else {
+        if (try_cycle) tok_scan_walk<true, false>(ld, round, cycle, len, from, runs, cap, true, out, cycles);
+        else tok_scan_walk<false, false>(ld, round, cycle, len, from, runs, cap, true, out, cycles);
+    }
+}
+
+// token_run_kernel's work on one job over host pointers: the same chunks to the same workgroups in the same order
+// (workgroup after workgroup: one of the orders the grid may take), every thread's count by the same helper, the same
+// early exits and the same minimum.  [*lo, *hi): the stream offsets that were loaded (when not null).
+int64_t run_find_host(const TokRunJob& J, uint32_t groups, int64_t* lo = nullptr, int64_t* hi = nullptr) {
+    int64_t l = INT64_MAX, h = INT64_MIN;
+    auto ld = [&](int64_t off) {
+        l = std::min(l, off);
+        h = std::max(h, off + 4);
+        return get_int(J.tokens + off);
+    };
+    const uint32_t per = J.v > 0 ? 1u : kScanMatchPer;
+    const int64_t C = tok_run_chunk_tokens(J.v), chunks = (J.max + C - 1) / C;
+    const uint32_t G = tok_run_groups(chunks, groups);
+    const uint64_t none = ~0ull, most = (uint64_t)J.max;
+    uint64_t word = none;
+    for (uint32_t g = 0; g < G; ++g) {
+        uint64_t mine = most;
+        for (int64_t k0 = g; k0 < chunks; k0 += (int64_t)kRunDepth * G) {
+            const uint64_t first = (uint64_t)(k0 * C);
+            if (first >= word || first >= mine) break;
+            uint64_t best = none;
+            for (uint32_t u = 0; u < kRunDepth; ++u) {
+                const int64_t k = k0 + (int64_t)u * G;
+                for (uint32_t t = 0; t < kRunThreads && k < chunks; ++t) {
+                    const uint32_t c = tok_run_lane(ld, J, k * C, t);
+                    if (c < per) best = std::min(best, (uint64_t)(k * C + (int64_t)per * t + c));
+                }
+            }
+            if (best != none) {
+                mine = std::min(mine, best);
+                break;
+            }
+        }
+        word = std::min(word, std::min(mine, most));
+    }
+    if (lo) *lo = l;
+    if (hi) *hi = h;
+    return (int64_t)std::min(word, most);
 }
 
 // token_unframe_kernel's work on one span, over host pointers: the same workgroup split, the same bytes one by one
@@ -632,28 +682,57 @@ void run_unspan_host(const UntokSpan& whole, const uint8_t** lo, const uint8_t**
 }
 
 // One launch of the walk into c->tok_runs, its TokScanOut and records copied to c->h_runs: two small downloads.
-int scan_device_runs(rsh_ctx* c, const uint8_t* d_tokens, int64_t len, int64_t from, int64_t cap, TokScanOut* out,
-                     const TokRun** runs, int64_t* cycles = nullptr) {
-    constexpr size_t kHead = 32;  // the TokScanOut and the cycles that cycle rounds proved, then the records
-    static_assert(sizeof(TokScanOut) + sizeof(int64_t) == kHead, "TokScanOut");
-    RSH_HIP(c->tok_runs.ensure(kHead + (size_t)cap * sizeof(TokRun)));
-    RSH_HIP(c->h_runs.ensure(kHead + (size_t)cap * sizeof(TokRun)));
+// The head of c->tok_runs and c->h_runs: the TokScanOut, the cycles that cycle rounds proved and the TokLong of a pass
+// that yields (option tokens_wide), then the records.
+constexpr size_t kRunsHead = 64;
+static_assert(sizeof(TokScanOut) + sizeof(int64_t) + sizeof(TokLong) == kRunsHead && sizeof(TokLong) == 32 &&
+                  sizeof(TokRunJob) == 40, "TokScanOut, TokLong, TokRunJob");
+constexpr size_t kLongAt = sizeof(TokScanOut) + sizeof(int64_t);
+
+// The launch of the walk into c->tok_runs and the download of the head: *out, and *lng when the pass yielded.
+int scan_device_head(rsh_ctx* c, const uint8_t* d_tokens, int64_t len, int64_t from, int64_t cap, int32_t wide,
+                     TokScanOut* out, int64_t* cycles, TokLong* lng) {
+    RSH_HIP(c->tok_runs.ensure(kRunsHead + (size_t)cap * sizeof(TokRun)));
+    RSH_HIP(c->h_runs.ensure(kRunsHead + (size_t)cap * sizeof(TokRun)));
     uint8_t* d = c->tok_runs.as<uint8_t>();
     uint8_t* hp = c->h_runs.as<uint8_t>();
-    RSH_HIP(launch_token_scan(d_tokens, len, from, reinterpret_cast<TokRun*>(d + kHead), cap,
+    RSH_HIP(launch_token_scan(d_tokens, len, from, reinterpret_cast<TokRun*>(d + kRunsHead), cap,
                               reinterpret_cast<TokScanOut*>(d), opt(OPT_TOKENS_CYCLE) != 0,
-                              reinterpret_cast<int64_t*>(d + sizeof(TokScanOut)), c->stream));
-    RSH_HIP(hipMemcpyAsync(hp, d, kHead, hipMemcpyDeviceToHost, c->stream));
+                              reinterpret_cast<int64_t*>(d + sizeof(TokScanOut)), c->stream, wide,
+                              reinterpret_cast<TokLong*>(d + kLongAt)));
+    RSH_HIP(hipMemcpyAsync(hp, d, wide > 0 ? kRunsHead : kLongAt, hipMemcpyDeviceToHost, c->stream));
     RSH_HIP(hipStreamSynchronize(c->stream));
     memcpy(out, hp, sizeof(TokScanOut));
     if (cycles) memcpy(cycles, hp + sizeof(TokScanOut), sizeof(int64_t));
     if (out->n < 0 || out->n > cap) return RSH_E_DEVICE;
-    if (out->n > 0) {
-        RSH_HIP(hipMemcpyAsync(hp + kHead, d + kHead, (size_t)out->n * sizeof(TokRun), hipMemcpyDeviceToHost, c->stream));
-        RSH_HIP(hipStreamSynchronize(c->stream));
-    }
-    *runs = reinterpret_cast<const TokRun*>(hp + kHead);
+    if (lng && wide > 0 && out->status == TOK_SCAN_LONG) memcpy(lng, hp + kLongAt, sizeof(TokLong));
     return RSH_OK;
+}
+// The pass's records copied to c->h_runs; with a job, the finder's launch before them and its result word's download
+// after: one synchronisation for all of it.
+int scan_device_fetch(rsh_ctx* c, int64_t n, const TokRunJob* job, uint32_t groups, TokLong* lng, const TokRun** runs) {
+    uint8_t* d = c->tok_runs.as<uint8_t>();
+    uint8_t* hp = c->h_runs.as<uint8_t>();
+    if (job) {
+        RSH_HIP(c->h_long.ensure(sizeof(TokRunJob)));
+        memcpy(c->h_long.p, job, sizeof(TokRunJob));
+        const int64_t C = tok_run_chunk_tokens(job->v);
+        RSH_HIP(launch_token_run(c->h_long.as<TokRunJob>(), 1, tok_run_groups((job->max + C - 1) / C, groups),
+                                 reinterpret_cast<TokLong*>(d + kLongAt), c->stream));
+        RSH_HIP(hipMemcpyAsync(hp + kLongAt, d + kLongAt, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (n > 0) RSH_HIP(hipMemcpyAsync(hp + kRunsHead, d + kRunsHead, (size_t)n * sizeof(TokRun), hipMemcpyDeviceToHost, c->stream));
+    if (job || n > 0) RSH_HIP(hipStreamSynchronize(c->stream));
+    if (job) memcpy(&lng->m, hp + kLongAt, sizeof(uint64_t));
+    *runs = reinterpret_cast<const TokRun*>(hp + kRunsHead);
+    return RSH_OK;
+}
+// One launch of the walk into c->tok_runs, its TokScanOut and records copied to c->h_runs: two small downloads.
+int scan_device_runs(rsh_ctx* c, const uint8_t* d_tokens, int64_t len, int64_t from, int64_t cap, TokScanOut* out,
+                     const TokRun** runs, int64_t* cycles = nullptr) {
+    const int rc = scan_device_head(c, d_tokens, len, from, cap, wide_opt(), out, cycles, nullptr);
+    if (rc != RSH_OK) return rc;
+    return scan_device_fetch(c, out->n, nullptr, 0, nullptr, runs);
 }
 
 // The launches of a resident plan: replica ranges and the literal runs the unframe kernel does not take as gather ops,
@@ -730,12 +809,18 @@ struct WalkBlock {
 
 // One launch of the segment's walk over the files live[0, nlive) of W.jobs[0, n), and the download of every file's
 // TokScanOut into W.outs (a file that did not walk keeps what `fill` left in its entry: 0xFF from the debug entry).
-int walk_round(rsh_ctx* c, const WalkBlock& W, size_t n, uint32_t nlive, bool fill) {
-    RSH_HIP(c->tokb_outs.ensure(n * sizeof(TokScanOut)));
+// Option tokens_wide > 0: the files' TokLongs lie behind the TokScanOuts in c->tokb_outs and come down with them, to
+// lngs (pinned, n entries) when it is not null.
+size_t tokb_long_at(size_t n) { return align16(n * sizeof(TokScanOut)); }
+int walk_round(rsh_ctx* c, const WalkBlock& W, size_t n, uint32_t nlive, bool fill, int32_t wide = wide_opt(),
+               TokLong* lngs = nullptr) {
+    RSH_HIP(c->tokb_outs.ensure(tokb_long_at(n) + (wide > 0 ? n * sizeof(TokLong) : 0)));
     TokScanOut* d_outs = c->tokb_outs.as<TokScanOut>();
+    TokLong* d_lngs = wide > 0 ? reinterpret_cast<TokLong*>(c->tokb_outs.as<uint8_t>() + tokb_long_at(n)) : nullptr;
     if (fill) RSH_HIP(hipMemsetAsync(d_outs, 0xFF, n * sizeof(TokScanOut), c->stream));
-    RSH_HIP(launch_token_scan_batch(W.jobs, W.live, nlive, d_outs, opt(OPT_TOKENS_CYCLE) != 0, c->stream));
+    RSH_HIP(launch_token_scan_batch(W.jobs, W.live, nlive, d_outs, opt(OPT_TOKENS_CYCLE) != 0, c->stream, wide, d_lngs));
     RSH_HIP(hipMemcpyAsync(W.outs, d_outs, n * sizeof(TokScanOut), hipMemcpyDeviceToHost, c->stream));
+    if (d_lngs && lngs) RSH_HIP(hipMemcpyAsync(lngs, d_lngs, n * sizeof(TokLong), hipMemcpyDeviceToHost, c->stream));
     RSH_HIP(hipStreamSynchronize(c->stream));
     return RSH_OK;
 }
@@ -748,60 +833,253 @@ struct ResFile {
         : job(j), plan(r.h, r.d_replica != nullptr, r.replica_len, r.defer_write != 0) {}
 };
 
+// ---- the walk's driver ----
+//
+// What runs the passes of a set of files: token_scan_kernel on one file, token_scan_batch_kernel on a segment's, or
+// the host stand-ins (the debug entry).  File k is an index into the driver's list.
+struct WalkFile {
+    const uint8_t* tokens;
+    int64_t len;
+};
+struct WalkStats {
+    int64_t passes = 0, rounds = 0, finds = 0, proved = 0;  // (every file's passes and rounds; finder launches; its tokens)
+};
+struct WalkBackend {
+    virtual ~WalkBackend() {}
+    virtual int64_t cap() const = 0;
+    // One pass of every file of `live` from from[k]: outs[k], and lng[k] of a file whose pass yielded.
+    virtual int pass(const std::vector<int32_t>& live, const std::vector<int64_t>& from, int32_t wide,
+                     std::vector<TokScanOut>& outs, std::vector<TokLong>& lng) = 0;
+    // The finder over jobs (job j's file is jobs[j].slot), all in one launch -- lng[slot].m -- and the records of the
+    // files of `live` brought to the host: one download round for both.
+    virtual int fetch(const std::vector<int32_t>& live, const std::vector<TokScanOut>& outs, const std::vector<TokRunJob>& jobs,
+                      uint32_t groups, std::vector<TokLong>& lng) = 0;
+    virtual TokRun* records(int32_t k) = 0;  // (the host copy: the driver extends a yielded record in place)
+};
+uint32_t run_groups_of(const std::vector<TokRunJob>& jobs, uint32_t groups) {
+    uint32_t G = 1;
+    for (const TokRunJob& J : jobs) {
+        const int64_t C = tok_run_chunk_tokens(J.v);
+        G = std::max(G, tok_run_groups((J.max + C - 1) / C, groups));
+    }
+    return G;
+}
+
+// The walk of files[0, n) to its end, the same for every backend: pass after pass over the files still walking; a file
+// whose pass yielded (TOK_SCAN_LONG) has its last record held back until the finder has extended it -- all the files
+// that yielded in a round share one finder launch -- and goes on behind the tokens proved.  sink(k, record) takes
+// file k's records in stream order (RunPlan::add, or a list); its first error, or a stream cut short after every
+// record before the cut, is file k's status, else end[k] is the byte after its putInt(0).  Returns other than RSH_OK
+// for a failure of the walk as a whole.  groups: the finder's workgroups per job (0: tok_run_groups' choice).
+template <class Sink>
+int walk_drive(WalkBackend& B, const std::vector<WalkFile>& files, const Sink& sink, std::vector<int64_t>& end,
+               std::vector<int>& status, WalkStats* st, uint32_t groups = 0) {
+    const size_t n = files.size();
+    const int32_t wide = wide_opt();
+    const int64_t cap = B.cap();
+    std::vector<int64_t> from(n, 0);
+    std::vector<TokScanOut> outs(n);
+    std::vector<TokLong> lng(n);
+    std::vector<TokRunJob> jobs;
+    std::vector<int32_t> live, next;
+    for (size_t k = 0; k < n; ++k) live.push_back((int32_t)k);
+    while (!live.empty()) {
+        const int rc = B.pass(live, from, wide, outs, lng);
+        if (rc != RSH_OK) return rc;
+        jobs.clear();
+        for (const int32_t k : live) {
+            const TokScanOut& so = outs[(size_t)k];
+            const bool more = so.status == TOK_SCAN_MORE || so.status == TOK_SCAN_LONG;
+            if (so.n < 0 || so.n > cap || (more && so.pos <= from[(size_t)k])) return RSH_E_DEVICE;
+            if (so.status == TOK_SCAN_LONG && (wide == 0 || so.n < 1)) return RSH_E_DEVICE;
+            ++st->passes;
+            st->rounds += so.rounds;
+            if (so.status != TOK_SCAN_LONG) continue;
+            TokRunJob J;
+            if (tok_run_job(files[(size_t)k].tokens, files[(size_t)k].len, so.pos, lng[(size_t)k].last, k, &J)) jobs.push_back(J);
+            else lng[(size_t)k].m = 0;  // the run cannot go on: nothing to launch
+        }
+        const int rf = B.fetch(live, outs, jobs, groups, lng);
+        if (rf != RSH_OK) return rf;
+        if (!jobs.empty()) ++st->finds;
+        for (const TokRunJob& J : jobs) lng[(size_t)J.slot].m = std::min<uint64_t>(lng[(size_t)J.slot].m, (uint64_t)J.max);
+        next.clear();
+        for (const int32_t k : live) {
+            const TokScanOut& so = outs[(size_t)k];
+            TokRun* runs = B.records(k);
+            int64_t resume = so.pos;
+            if (so.status == TOK_SCAN_LONG) {
+                TokRun& last = runs[so.n - 1];
+                if (memcmp(&last, &lng[(size_t)k].last, sizeof(TokRun)) != 0) return RSH_E_DEVICE;
+                const int64_t m = (int64_t)lng[(size_t)k].m;
+                last.count += m;
+                st->proved += m;
+                resume += m * tok_run_stride(last);
+            }
+            int rp = RSH_OK;
+            for (int64_t i = 0; i < so.n && rp == RSH_OK; ++i) rp = sink(k, runs[i]);
+            // (cut short: after every token before the cut was planned)
+            if (rp == RSH_OK && so.status != TOK_SCAN_MORE && so.status != TOK_SCAN_END && so.status != TOK_SCAN_LONG)
+                rp = RSH_E_INVAL;
+            if (rp != RSH_OK) {
+                status[(size_t)k] = rp;
+                end[(size_t)k] = so.pos;  // (a stream cut short: the offending token)
+            } else if (so.status == TOK_SCAN_END) {
+                end[(size_t)k] = so.pos;
+            } else {
+                from[(size_t)k] = resume;
+                next.push_back(k);
+            }
+        }
+        live.swap(next);
+    }
+    return RSH_OK;
+}
+
+// token_scan_kernel on one file (rsh_receiver_combine_resident).
+struct OneWaveWalk : WalkBackend {
+    rsh_ctx* c;
+    WalkFile f;
+    int64_t cap_;
+    const TokRun* got = nullptr;
+    OneWaveWalk(rsh_ctx* cc, WalkFile ff, int64_t cp) : c(cc), f(ff), cap_(cp) {}
+    int64_t cap() const override { return cap_; }
+    int pass(const std::vector<int32_t>&, const std::vector<int64_t>& from, int32_t wide, std::vector<TokScanOut>& outs,
+             std::vector<TokLong>& lng) override {
+        return scan_device_head(c, f.tokens, f.len, from[0], cap_, wide, &outs[0], nullptr, &lng[0]);
+    }
+    int fetch(const std::vector<int32_t>&, const std::vector<TokScanOut>& outs, const std::vector<TokRunJob>& jobs,
+              uint32_t groups, std::vector<TokLong>& lng) override {
+        return scan_device_fetch(c, outs[0].n, jobs.empty() ? nullptr : &jobs[0], groups, &lng[0], &got);
+    }
+    TokRun* records(int32_t) override { return const_cast<TokRun*>(got); }
+};
+
+// token_scan_batch_kernel on a segment's files (rsh_receiver_combine_batch_resident): a round is the walk's launch and
+// one download, then the records' copy launch -- with the finder's launch and its words' download when files yielded
+// -- and one more synchronisation, whatever the file count.
+struct SegmentWalk : WalkBackend {
+    rsh_ctx* c;
+    const std::vector<WalkFile>& files;
+    int64_t cap_;
+    size_t n, stride;
+    uint8_t* d_runs = nullptr;
+    uint8_t* h_runs = nullptr;
+    TokLong* h_lng = nullptr;   // c->h_long: n TokLongs, then the finder's descriptors
+    TokRunJob* h_jobs = nullptr;
+    SegmentWalk(rsh_ctx* cc, const std::vector<WalkFile>& ff, int64_t cp)
+        : c(cc), files(ff), cap_(cp), n(ff.size()), stride(align16((size_t)cp * sizeof(TokRun))) {}
+    int64_t cap() const override { return cap_; }
+    int init() {
+        // (the copy kernel's destinations are 16-byte aligned)
+        RSH_HIP(c->tokb_runs.ensure(n * stride));
+        RSH_HIP(c->h_tokb_runs.ensure(n * stride));
+        RSH_HIP(c->h_tokb.ensure(WalkBlock::bytes(n)));
+        if (wide_opt() > 0) {
+            RSH_HIP(c->h_long.ensure(n * (sizeof(TokLong) + sizeof(TokRunJob))));
+            h_lng = c->h_long.as<TokLong>();
+            h_jobs = reinterpret_cast<TokRunJob*>(h_lng + n);
+        }
+        d_runs = c->tokb_runs.as<uint8_t>();
+        h_runs = c->h_tokb_runs.as<uint8_t>();
+        const WalkBlock W(c->h_tokb.as<uint8_t>(), n);
+        for (size_t k = 0; k < n; ++k)
+            W.jobs[k] = TokScanJob{files[k].tokens, files[k].len, 0, reinterpret_cast<TokRun*>(d_runs + k * stride), cap_};
+        return RSH_OK;
+    }
+    int pass(const std::vector<int32_t>& live, const std::vector<int64_t>& from, int32_t wide, std::vector<TokScanOut>& outs,
+             std::vector<TokLong>& lng) override {
+        const WalkBlock W(c->h_tokb.as<uint8_t>(), n);
+        for (const int32_t k : live) W.jobs[k].from = from[(size_t)k];
+        memcpy(W.live, live.data(), live.size() * sizeof(int32_t));
+        const int rc = walk_round(c, W, n, (uint32_t)live.size(), false, wide, h_lng);
+        if (rc != RSH_OK) return rc;
+        for (const int32_t k : live) {
+            outs[(size_t)k] = W.outs[k];
+            if (wide > 0 && W.outs[k].status == TOK_SCAN_LONG) lng[(size_t)k] = h_lng[k];
+        }
+        return RSH_OK;
+    }
+    int fetch(const std::vector<int32_t>& live, const std::vector<TokScanOut>& outs, const std::vector<TokRunJob>& jobs,
+              uint32_t groups, std::vector<TokLong>& lng) override {
+        const WalkBlock W(c->h_tokb.as<uint8_t>(), n);
+        if (!jobs.empty()) {
+            TokLong* d_lngs = reinterpret_cast<TokLong*>(c->tokb_outs.as<uint8_t>() + tokb_long_at(n));
+            memcpy(h_jobs, jobs.data(), jobs.size() * sizeof(TokRunJob));
+            const uint32_t G = run_groups_of(jobs, groups);
+            for (size_t at = 0; at < jobs.size(); at += 65535)  // (a grid's second dimension)
+                RSH_HIP(launch_token_run(h_jobs + at, (uint32_t)std::min<size_t>(65535, jobs.size() - at), G, d_lngs, c->stream));
+            RSH_HIP(hipMemcpyAsync(h_lng, d_lngs, n * sizeof(TokLong), hipMemcpyDeviceToHost, c->stream));
+        }
+        uint32_t nent = 0;
+        int64_t max_len = 0;
+        for (const int32_t k : live) {
+            const TokScanOut& so = outs[(size_t)k];
+            if (so.n == 0) continue;
+            const int64_t bytes = so.n * (int64_t)sizeof(TokRun);
+            W.ents[nent++] = CopyEnt{d_runs + (size_t)k * stride, h_runs + (size_t)k * stride, bytes};
+            max_len = std::max(max_len, bytes);
+        }
+        RSH_HIP(launch_copy_many(W.ents, nent, max_len, c->stream));
+        RSH_HIP(hipStreamSynchronize(c->stream));
+        for (const TokRunJob& J : jobs) lng[(size_t)J.slot].m = h_lng[J.slot].m;
+        return RSH_OK;
+    }
+    TokRun* records(int32_t k) override { return reinterpret_cast<TokRun*>(h_runs + (size_t)k * stride); }
+};
+
+// The host stand-ins with rounds `lanes` lanes wide (the debug entry).
+struct HostWalk : WalkBackend {
+    const std::vector<WalkFile>& files;
+    int64_t cap_;
+    uint32_t lanes;
+    std::vector<std::vector<TokRun>> runs;
+    HostWalk(const std::vector<WalkFile>& ff, int64_t cp, uint32_t ln)
+        : files(ff), cap_(cp), lanes(ln), runs(ff.size(), std::vector<TokRun>((size_t)cp)) {}
+    int64_t cap() const override { return cap_; }
+    int pass(const std::vector<int32_t>& live, const std::vector<int64_t>& from, int32_t wide, std::vector<TokScanOut>& outs,
+             std::vector<TokLong>& lng) override {
+        for (const int32_t k : live)
+            scan_host(files[(size_t)k].tokens, files[(size_t)k].len, from[(size_t)k], runs[(size_t)k].data(), cap_, &outs[(size_t)k],
+                      lanes, opt(OPT_TOKENS_CYCLE) != 0, nullptr, wide, &lng[(size_t)k]);
+        return RSH_OK;
+    }
+    int fetch(const std::vector<int32_t>&, const std::vector<TokScanOut>&, const std::vector<TokRunJob>& jobs, uint32_t groups,
+              std::vector<TokLong>& lng) override {
+        const uint32_t G = run_groups_of(jobs, groups);  // (one launch: every job at the same grid width)
+        for (const TokRunJob& J : jobs) lng[(size_t)J.slot].m = (uint64_t)run_find_host(J, G);
+        return RSH_OK;
+    }
+    TokRun* records(int32_t k) override { return runs[(size_t)k].data(); }
+};
+
+void keep_walk_stats(rsh_ctx* c, const WalkStats& st) {
+    c->walk_stats[0] = st.passes;
+    c->walk_stats[1] = st.rounds;
+    c->walk_stats[2] = st.finds;
+    c->walk_stats[3] = st.proved;
+}
+
 // The walk rounds of files[0, n): on return every file's plan is complete and end[k] the byte after its putInt(0), or
 // jobs[files[k].job].status holds its error.  Returns other than RSH_OK for a failure of the call as a whole.
 int walk_files(rsh_ctx* c, rsh_resident_job* jobs, std::vector<std::unique_ptr<ResFile>>& files, std::vector<int64_t>& end) {
     const size_t n = files.size();
     const int64_t cap = std::min<int64_t>(std::max<int64_t>(opt(OPT_TOKENS_RUNS_BATCH), 1), 1 << 24);
-    const size_t stride = align16((size_t)cap * sizeof(TokRun));  // (the copy kernel's destinations are 16-byte aligned)
-    RSH_HIP(c->tokb_runs.ensure(n * stride));
-    RSH_HIP(c->h_tokb_runs.ensure(n * stride));
-    RSH_HIP(c->h_tokb.ensure(WalkBlock::bytes(n)));
-    const WalkBlock W(c->h_tokb.as<uint8_t>(), n);
-    uint8_t* const d_runs = c->tokb_runs.as<uint8_t>();
-    const uint8_t* const h_runs = c->h_tokb_runs.as<uint8_t>();
-    std::vector<int32_t> live;
+    std::vector<WalkFile> wf;
     for (size_t k = 0; k < n; ++k) {
         const rsh_resident_job& j = jobs[files[k]->job];
-        W.jobs[k] = TokScanJob{static_cast<const uint8_t*>(j.d_tokens), j.tokens_len, 0,
-                               reinterpret_cast<TokRun*>(d_runs + k * stride), cap};
-        live.push_back((int32_t)k);
+        wf.push_back(WalkFile{static_cast<const uint8_t*>(j.d_tokens), j.tokens_len});
     }
-    while (!live.empty()) {
-        memcpy(W.live, live.data(), live.size() * sizeof(int32_t));
-        const int rc = walk_round(c, W, n, (uint32_t)live.size(), false);
-        if (rc != RSH_OK) return rc;
-        uint32_t nent = 0;
-        int64_t max_len = 0;
-        for (const int32_t k : live) {
-            const TokScanOut& so = W.outs[k];
-            if (so.n < 0 || so.n > cap || (so.status == TOK_SCAN_MORE && so.pos <= W.jobs[k].from)) return RSH_E_DEVICE;
-            if (so.n == 0) continue;
-            const int64_t bytes = so.n * (int64_t)sizeof(TokRun);
-            W.ents[nent++] = CopyEnt{d_runs + (size_t)k * stride, const_cast<uint8_t*>(h_runs) + (size_t)k * stride, bytes};
-            max_len = std::max(max_len, bytes);
-        }
-        RSH_HIP(launch_copy_many(W.ents, nent, max_len, c->stream));
-        RSH_HIP(hipStreamSynchronize(c->stream));
-        std::vector<int32_t> next;
-        for (const int32_t k : live) {
-            const TokScanOut& so = W.outs[k];
-            const TokRun* runs = reinterpret_cast<const TokRun*>(h_runs + (size_t)k * stride);
-            int rp = RSH_OK;
-            for (int64_t i = 0; i < so.n && rp == RSH_OK; ++i) rp = files[(size_t)k]->plan.add(runs[i]);
-            // (cut short: after every token before the cut was planned)
-            if (rp == RSH_OK && so.status != TOK_SCAN_MORE && so.status != TOK_SCAN_END) rp = RSH_E_INVAL;
-            if (rp != RSH_OK) {
-                jobs[files[(size_t)k]->job].status = rp;
-            } else if (so.status == TOK_SCAN_MORE) {
-                W.jobs[k].from = so.pos;
-                next.push_back(k);
-            } else {
-                end[(size_t)k] = so.pos;
-            }
-        }
-        live.swap(next);
-    }
+    SegmentWalk B(c, wf, cap);
+    const int ri = B.init();
+    if (ri != RSH_OK) return ri;
+    std::vector<int> status(n, RSH_OK);
+    WalkStats st;
+    const int rc = walk_drive(B, wf, [&](int32_t k, const TokRun& r) { return files[(size_t)k]->plan.add(r); }, end, status, &st);
+    keep_walk_stats(c, st);
+    if (rc != RSH_OK) return rc;
+    for (size_t k = 0; k < n; ++k)
+        if (status[k] != RSH_OK) jobs[files[k]->job].status = status[k];
     return RSH_OK;
 }
 
@@ -987,20 +1265,18 @@ int rsh_receiver_combine_resident(rsh_ctx* ctx, const void* d_tokens, int64_t to
     // the walk and the plan: every run is validated before anything reads through it
     RunPlan P(*h, d_replica != nullptr, replica_len, defer_write != 0);
     const int64_t cap = std::min<int64_t>(std::max<int64_t>(opt(OPT_TOKENS_RUNS), 1), 1 << 24);
-    TokScanOut so{0, 0, TOK_SCAN_MORE, 0};
-    while (so.status == TOK_SCAN_MORE) {
-        const TokRun* runs = nullptr;
-        const int rc = scan_device_runs(ctx, tok, tokens_len, so.pos, cap, &so, &runs);
-        if (rc != RSH_OK) return rc;
-        for (int64_t i = 0; i < so.n; ++i) {
-            const int rp = P.add(runs[i]);
-            if (rp != RSH_OK) return rp;
-        }
-    }
-    if (so.status != TOK_SCAN_END) return RSH_E_INVAL;  // cut short, after every token before the cut was planned
+    const std::vector<WalkFile> wf{WalkFile{tok, tokens_len}};
+    OneWaveWalk B(ctx, wf[0], cap);
+    std::vector<int64_t> end(1, 0);
+    std::vector<int> status(1, RSH_OK);
+    WalkStats st;
+    const int rc = walk_drive(B, wf, [&](int32_t, const TokRun& r) { return P.add(r); }, end, status, &st);
+    keep_walk_stats(ctx, st);
+    if (rc != RSH_OK) return rc;
+    if (status[0] != RSH_OK) return status[0];  // (cut short: RSH_E_INVAL after every token before the cut was planned)
     const int rf = P.finish();
     if (rf != RSH_OK) return rf;
-    out->tokens_used = so.pos;
+    out->tokens_used = end[0];
     out->target_len = P.intact ? 0 : P.target_len;
     out->literal = P.literal;
     out->matched = P.matched;
@@ -1119,6 +1395,100 @@ int rsh_debug_tokens_scan_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t 
                                    rsh_token_run* runs, int64_t cap, int64_t* n_runs, int64_t* pos, int32_t* status) {
     return rsh_debug_tokens_scan_rounds_selftest(ctx, tokens, tokens_len, from, runs, cap, n_runs, pos, status, nullptr,
                                                  nullptr);
+}
+
+namespace {
+thread_local int64_t g_run_lo = 0, g_run_hi = 0;  // rsh_debug_tokens_run_extent
+}
+
+int rsh_debug_tokens_run_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t pos, int32_t v,
+                                  int64_t max, int32_t groups, int64_t* m) {
+    if (!tokens || !m || tokens_len < 0 || pos < 0 || pos > tokens_len || v == 0 || max < 0 || groups < 0 ||
+        groups > (int32_t)kRunMaxGroups)
+        return RSH_E_INVAL;
+    *m = 0;
+    g_run_lo = g_run_hi = 0;
+    const TokRunJob J{tokens, tokens_len, pos, v, 0, std::min(max, tok_run_max(tokens_len, pos, v))};
+    if (J.max == 0) return RSH_OK;
+    if (!ctx) {
+        *m = run_find_host(J, (uint32_t)groups, &g_run_lo, &g_run_hi);
+        return RSH_OK;
+    }
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    RSH_HIP(ctx->tok_runs.ensure(kRunsHead));
+    RSH_HIP(ctx->h_runs.ensure(kRunsHead));
+    TokLong* d = reinterpret_cast<TokLong*>(ctx->tok_runs.as<uint8_t>() + kLongAt);
+    RSH_HIP(hipMemsetAsync(d, 0xFF, sizeof(uint64_t), ctx->stream));
+    TokLong got{0, TokRun{0, 0, 0, 0}};
+    const TokRun* none = nullptr;
+    const int rc = scan_device_fetch(ctx, 0, &J, (uint32_t)groups, &got, &none);
+    if (rc != RSH_OK) return rc;
+    *m = (int64_t)std::min<uint64_t>(got.m, (uint64_t)J.max);
+    return RSH_OK;
+}
+
+int rsh_debug_tokens_run_extent(int64_t* lo, int64_t* hi) {
+    if (!lo || !hi) return RSH_E_INVAL;
+    *lo = g_run_lo;
+    *hi = g_run_hi;
+    return RSH_OK;
+}
+
+int rsh_debug_tokens_walk_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t cap, int32_t lanes,
+                                   rsh_token_run* runs, int64_t max_runs, int64_t* n_runs, int64_t* pos, int32_t* status,
+                                   int64_t stats[4]) {
+    if (!tokens || tokens_len < 0 || cap < 1 || cap > (1 << 24) || max_runs < 0 || (max_runs > 0 && !runs) || !n_runs || !pos ||
+        !status)
+        return RSH_E_INVAL;
+    if (lanes == 0) lanes = (int32_t)kScanLanes;
+    if (lanes < (int32_t)kScanLanes || lanes % (int32_t)kScanLanes || lanes > (int32_t)(kScanLanes * kScanMaxWaves)) return RSH_E_INVAL;
+    if (ctx && lanes != (int32_t)kScanLanes && lanes != (int32_t)(kScanLanes * kScanBatchWaves)) return RSH_E_INVAL;  // the kernels' widths
+    const std::vector<WalkFile> wf{WalkFile{tokens, tokens_len}};
+    std::vector<int64_t> end(1, 0);
+    std::vector<int> st(1, RSH_OK);
+    WalkStats ws;
+    int64_t n = 0;
+    auto sink = [&](int32_t, const TokRun& r) {
+        if (n < max_runs) memcpy(&runs[n], &r, sizeof(TokRun));
+        ++n;
+        return (int)RSH_OK;
+    };
+    int rc;
+    if (!ctx) {
+        HostWalk B(wf, cap, (uint32_t)lanes);
+        rc = walk_drive(B, wf, sink, end, st, &ws);
+    } else {
+        RSH_CLAIM(ctx);
+        RSH_HIP(hipSetDevice(ctx->device));
+        if (lanes == (int32_t)kScanLanes) {
+            OneWaveWalk B(ctx, wf[0], cap);
+            rc = walk_drive(B, wf, sink, end, st, &ws);
+        } else {
+            SegmentWalk B(ctx, wf, cap);
+            rc = B.init();
+            if (rc == RSH_OK) rc = walk_drive(B, wf, sink, end, st, &ws);
+        }
+        keep_walk_stats(ctx, ws);
+    }
+    if (rc != RSH_OK) return rc;
+    *n_runs = n;
+    *pos = end[0];
+    *status = st[0] == RSH_OK ? (int32_t)TOK_SCAN_END : st[0];
+    if (stats) {
+        stats[0] = ws.passes;
+        stats[1] = ws.rounds;
+        stats[2] = ws.finds;
+        stats[3] = ws.proved;
+    }
+    return n > max_runs ? RSH_E_NOSPACE : RSH_OK;
+}
+
+int rsh_debug_walk_stats(rsh_ctx* ctx, int64_t stats[4]) {
+    if (!ctx || !stats) return RSH_E_INVAL;
+    RSH_CLAIM(ctx);
+    memcpy(stats, ctx->walk_stats, sizeof(ctx->walk_stats));
+    return RSH_OK;
 }
 
 int rsh_debug_untokens_selftest(rsh_ctx* ctx, const uint8_t* tokens, int64_t tokens_len, int64_t pos, int32_t T,

@@ -35,9 +35,11 @@ struct TokRun {
     int32_t v;      // LITERAL: the tokens' length; MATCH: the first block index
     int64_t count;  // tokens
 };
-enum { TOK_SCAN_MORE = 0, TOK_SCAN_END = 1 };  // (or RSH_E_INVAL: the stream is cut short at pos)
+// (or RSH_E_INVAL: the stream is cut short at pos).  LONG (option tokens_wide): the pass yields on a long run -- the
+// last record listed is the run so far and pos the next token start, which no round has read ("Wide rounds" below).
+enum { TOK_SCAN_MORE = 0, TOK_SCAN_END = 1, TOK_SCAN_LONG = 2 };
 struct TokScanOut {
-    int64_t pos;     // END: the byte after putInt(0); MORE: the first token not listed; RSH_E_INVAL: the offending token
+    int64_t pos;     // END: the byte after putInt(0); MORE, LONG: the first token not listed; RSH_E_INVAL: the offending token
     int64_t n;       // records written
     int32_t status;
     int32_t rounds;  // plain rounds plus cycle attempts of this pass
@@ -247,6 +249,85 @@ RSH_HD void tok_shape_cycles(TokShape* S, int64_t P, int64_t m) {
     for (int i = 0; i < kCycleHistory; ++i) S[i].pos += (m - pushed) * P;
 }
 
+// ---- wide rounds ----
+//
+// One long run (an unchanged file's consecutive match tokens, a new file's equal-length literal tokens) gives the walk
+// a chain of dependent rounds, each one wave or one workgroup wide.  Once the run's shape is known the rest of it is
+// independent work: token j of a literal run of length T that continues at pos has its header at pos + j (T + 4), token
+// j of a match run is the int at pos + 4 j and must be v - j, and the run ends at the smallest j that fails -- a
+// grid-wide minimum, not a chain.  The rule (option tokens_wide = K > 0; kWide picks the instantiation as kCycle does):
+//   * the walk counts a streak of consecutive plain rounds that each proved the round's full width (width x per
+//     tokens); a round that is not full, and a cycle round, reset it; when the streak reaches K the pass ends with
+//     TOK_SCAN_LONG: pos is the next token start, the last record the run so far, and the writer leaves that record
+//     and an all-ones result word in *lng;
+//   * the host launches token_run_kernel for that record (TokRunJob), adds the tokens it proved to the record's count
+//     before the record is planned, and resumes the walk behind them.  What the finder proves is maximal -- its test is
+//     tok_scan_lane's, the walk's own -- so the next pass starts a fresh record and the records are the plain walk's;
+//   * errors and the stream's end are found by the plain walk alone: the finder only stops in front of them.
+// The finder works in chunks of kRunThreads lanes (256 literal tokens, 4096 match tokens): tok_run_chunk re-bases the
+// run on a chunk's first token and thread t plays lane t of tok_scan_lane, so every offset is the walk's arithmetic.
+struct TokLong {
+    unsigned long long m;  // the finder's result word: all ones from the walk, then the smallest failing token
+    TokRun last;           // the record a pass that ended LONG yields (a copy of its last record)
+};
+struct TokRunJob {
+    const uint8_t* tokens;
+    int64_t len;
+    int64_t pos;   // a token start
+    int32_t v;     // what a continuing token holds at pos: LITERAL: T; MATCH: ~(first + count) of the record extended
+    int32_t slot;  // the job's result is res[slot].m
+    int64_t max;   // tokens examined at most (> 0): the result is the smallest failing token's index, or max
+};
+constexpr uint32_t kRunThreads = 256;
+constexpr uint32_t kRunDepth = 4;        // chunks whose loads a thread has in flight together
+constexpr uint32_t kRunMaxGroups = 1024;  // workgroups of one job at most
+RSH_HD int64_t tok_run_chunk_tokens(int32_t v) { return (int64_t)kRunThreads * (v > 0 ? 1u : kScanMatchPer); }
+// The most tokens the stream can hold from pos on, and no more than a match run has before its index passes INT32_MAX.
+RSH_HD int64_t tok_run_max(int64_t len, int64_t pos, int32_t v) {
+    if (pos < 0 || pos > len) return 0;
+    const int64_t room = v > 0 ? (len - pos) / ((int64_t)v + 4) : (len - pos) / 4;
+    return v > 0 || room < (1ll << 31) ? room : (1ll << 31);
+}
+struct TokRunChunk {
+    int64_t pos;
+    int32_t v;
+};
+RSH_HD TokRunChunk tok_run_chunk(int64_t pos, int32_t v, int64_t first_token) {
+    if (v > 0) return TokRunChunk{pos + first_token * ((int64_t)v + 4), v};
+    return TokRunChunk{pos + 4 * first_token, (int32_t)((uint32_t)v - (uint32_t)first_token)};
+}
+// Thread t's leading count in the chunk whose first token is first_token (tok_scan_lane's: 0 or 1; 0 .. 16).  A match
+// run whose expected int has turned non-negative at the chunk's first token has no further token (and such a value
+// must not reach tok_scan_lane, which would take it for a literal length).
+template <class Load>
+RSH_HD uint32_t tok_run_lane(const Load& ld, const TokRunJob& J, int64_t first_token, uint32_t t) {
+    const TokRunChunk C = tok_run_chunk(J.pos, J.v, first_token);
+    if (J.v < 0 && C.v >= 0) return 0u;
+    return tok_scan_lane(ld, C.pos, J.len, C.v, t);
+}
+// Workgroups of a job: a thread's kRunDepth chunks to each, kRunMaxGroups at most (groups > 0: forced).
+RSH_HD uint32_t tok_run_groups(int64_t chunks, uint32_t groups) {
+    if (groups > 0) return groups < kRunMaxGroups ? groups : kRunMaxGroups;
+    const int64_t g = (chunks + kRunDepth - 1) / kRunDepth;
+    return (uint32_t)(g < 1 ? 1 : g > (int64_t)kRunMaxGroups ? (int64_t)kRunMaxGroups : g);
+}
+// The finder's job for the record a pass yielded at pos; false: nothing to launch (the run cannot go on).
+RSH_HD bool tok_run_job(const uint8_t* tokens, int64_t len, int64_t pos, const TokRun& last, int32_t slot, TokRunJob* J) {
+    int32_t v;
+    if (last.kind == RSH_EV_LITERAL) {
+        v = last.v;
+    } else {
+        const int64_t next = (int64_t)last.v + last.count;
+        if (next > (int64_t)INT32_MAX) return false;
+        v = ~(int32_t)next;
+    }
+    const int64_t max = tok_run_max(len, pos, v);
+    if (max <= 0) return false;
+    *J = TokRunJob{tokens, len, pos, v, slot, max};
+    return true;
+}
+RSH_HD int64_t tok_run_stride(const TokRun& r) { return r.kind == RSH_EV_LITERAL ? (int64_t)r.v + 4 : 4; }
+
 // The walk from stream offset `from`: at most cap records.  head(pos): the int at pos, the same value in every lane;
 // round(pos, v): the tokens of the run that starts at pos proven in one round (>= 1: the caller of round has checked
 // the first token), the same value in every lane -- the host stand-in loops over the lanes, the kernel ballots.
@@ -255,11 +336,14 @@ RSH_HD void tok_shape_cycles(TokShape* S, int64_t P, int64_t m) {
 // last one; attempted when kCycle (option tokens_cycle picks the instantiation: with kCycle false the walk is the plain
 // walk's code and nothing else).  writer: this lane stores the records and *out (rounds: the
 // plain rounds plus the cycle attempts), and *cycles, the cycles that cycle rounds proved, when it is not null.
-template <bool kCycle, class Head, class Round, class Cycle>
+// kWide (option tokens_wide > 0): the pass yields after `wide` full rounds of `width` lanes in a row (wide rounds,
+// above) and the writer fills *lng; with kWide false neither is read and the walk's code is what it was without them.
+template <bool kCycle, bool kWide, class Head, class Round, class Cycle>
 RSH_HD void tok_scan_walk(const Head& head, const Round& round, const Cycle& cycle, int64_t len,
-                          int64_t from, TokRun* runs, int64_t cap, bool writer, TokScanOut* out, int64_t* cycles) {
+                          int64_t from, TokRun* runs, int64_t cap, bool writer, TokScanOut* out, int64_t* cycles,
+                          int32_t wide = 0, uint32_t width = 0, TokLong* lng = nullptr) {
     int64_t pos = from, n = 0, proven = 0;
-    int32_t status, rounds = 0;
+    int32_t status, rounds = 0, streak = 0;
     TokRun last = {0, 0, 0, 0};
     TokShape S[kCycleHistory];  // S[i]: record n - 1 - i of this pass (S[0] is `last`, whose count may still grow)
 #if defined(__HIPCC__)
@@ -305,6 +389,7 @@ RSH_HD void tok_scan_walk(const Head& head, const Round& round, const Cycle& cyc
                     proven += m;
                     if (writer) runs[n - 1] = last;
                     pos += m * T.P;
+                    if (kWide) streak = 0;
                     continue;  // (the token there is read as any other: it may extend `last`)
                 }
             }
@@ -320,10 +405,18 @@ RSH_HD void tok_scan_walk(const Head& head, const Round& round, const Cycle& cyc
         }
         if (writer) runs[n - 1] = last;
         pos += v > 0 ? m * ((int64_t)v + 4) : 4 * m;
+        if (kWide) {
+            streak = m == (int64_t)width * (v > 0 ? 1u : kScanMatchPer) ? streak + 1 : 0;
+            if (streak >= wide) {
+                status = TOK_SCAN_LONG;
+                break;
+            }
+        }
     }
     if (writer) {
         *out = TokScanOut{pos, n, status, rounds};
         if (cycles) *cycles = proven;
+        if (kWide && status == TOK_SCAN_LONG) *lng = TokLong{~0ull, last};
     }
 }
 

@@ -215,7 +215,7 @@ class TokenScanJob(ctypes.Structure):
 
 
 COMBINE_NO_MD5 = 1
-SCAN_MORE, SCAN_END = 0, 1
+SCAN_MORE, SCAN_END, SCAN_LONG = 0, 1, 2
 
 EVENT_DTYPE = np.dtype([("offset", "<i8"), ("length", "<i8"), ("kind", "<i4"), ("index", "<i4"),
                         ("count", "<i4"), ("reserved", "<i4")])
@@ -241,7 +241,8 @@ DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_rese
                  "rsh_debug_phase_round_b", "rsh_debug_phase_segments", "rsh_debug_k1_plan",
                  "rsh_debug_k1_plan_batch", "rsh_debug_md5_device_selftest", "rsh_debug_md5_closing",
                  "rsh_debug_md5_plan", "rsh_debug_io_selftest", "rsh_debug_window_weak_selftest",
-                 "rsh_debug_tokens_scan_rounds_selftest"]
+                 "rsh_debug_tokens_scan_rounds_selftest", "rsh_debug_tokens_run_selftest",
+                 "rsh_debug_tokens_run_extent", "rsh_debug_tokens_walk_selftest", "rsh_debug_walk_stats"]
 
 _LIB = None
 
@@ -371,6 +372,11 @@ def lib():
         "rsh_debug_tokens_scan_rounds_selftest": ([P, P, I64, I64, ctypes.POINTER(TokenRun), I64, ctypes.POINTER(I64),
                                                    ctypes.POINTER(I64), ctypes.POINTER(I32), ctypes.POINTER(I64),
                                                    ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_debug_tokens_run_selftest": ([P, P, I64, I64, I32, I64, I32, ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_debug_tokens_run_extent": ([ctypes.POINTER(I64), ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_debug_tokens_walk_selftest": ([P, P, I64, I64, I32, ctypes.POINTER(TokenRun), I64, ctypes.POINTER(I64),
+                                            ctypes.POINTER(I64), ctypes.POINTER(I32), ctypes.POINTER(I64)], ctypes.c_int),
+        "rsh_debug_walk_stats": ([P, ctypes.POINTER(I64)], ctypes.c_int),
         "rsh_debug_untokens_selftest": ([P, P, I64, I64, I32, I64, P, I64, ctypes.POINTER(I64), ctypes.POINTER(I64),
                                          ctypes.POINTER(I64)], ctypes.c_int),
         "rsh_tokens_frame_batch_device": ([P, ctypes.POINTER(TokenFrameJob), I32], ctypes.c_int),
@@ -598,6 +604,44 @@ def tokens_scan_batch_selftest(jobs, live=None, lanes=0, ctx=None, rounds=False)
         return [(tj[i].n_runs, tj[i].pos, tj[i].status) + more(i) for i in range(n)]
     return [([(r.pos, r.kind, r.value, r.count) for r in keep[i][:tj[i].n_runs]] if tj[i].n_runs >= 0 else None,
              tj[i].pos, tj[i].status) + more(i) for i in range(n)]
+
+
+def tokens_run_selftest(tokens, length, pos, v, max_tokens, groups=0, ctx=None):
+    """rsh_debug_tokens_run_selftest: the run finder alone -- how many further tokens continue a run from the token
+    start pos where a continuing token holds v (a literal run's T, a match run's ~(first + count)), examining at most
+    max_tokens.  ctx None: tokens is a uint8 array and the host stand-in runs: (m, lowest stream offset loaded, one
+    past the highest).  With a Context: a DeviceBuffer or device address and token_run_kernel: m alone.  groups 0: the
+    production choice of workgroups; else forced."""
+    m = ctypes.c_int64()
+    _check(lib().rsh_debug_tokens_run_selftest(None if ctx is None else ctx.handle, _addr(tokens), length, pos, v,
+                                               max_tokens, groups, ctypes.byref(m)))
+    if ctx is not None:
+        return m.value
+    lo, hi = ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().rsh_debug_tokens_run_extent(ctypes.byref(lo), ctypes.byref(hi)))
+    return m.value, lo.value, hi.value
+
+
+def tokens_walk_selftest(tokens, length, cap=1 << 16, lanes=64, max_runs=1 << 16, ctx=None):
+    """rsh_debug_tokens_walk_selftest: a whole walk to its end through the resident Receivers' driver under the options
+    as they stand: ([(pos, kind, value, count)], end position, status SCAN_END / RSH_E_INVAL, (passes, rounds, finder
+    launches, tokens the finder proved)).  ctx None: a uint8 array and the stand-ins at `lanes` lanes; with a Context
+    a device address and token_scan_kernel (lanes 64) or token_scan_batch_kernel (256)."""
+    runs = (TokenRun * max(max_runs, 1))()
+    n, pos, st = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+    stats = (ctypes.c_int64 * 4)()
+    _check(lib().rsh_debug_tokens_walk_selftest(None if ctx is None else ctx.handle, _addr(tokens), length, cap, lanes,
+                                                runs, max_runs, ctypes.byref(n), ctypes.byref(pos), ctypes.byref(st),
+                                                stats))
+    return [(r.pos, r.kind, r.value, r.count) for r in runs[:n.value]], pos.value, st.value, tuple(stats)
+
+
+def walk_stats(ctx):
+    """rsh_debug_walk_stats: (passes, rounds, finder launches, tokens the finder proved) of the walk of the context's
+    last resident Receiver call."""
+    stats = (ctypes.c_int64 * 4)()
+    _check(lib().rsh_debug_walk_stats(ctx.handle, stats))
+    return tuple(stats)
 
 
 def untokens_selftest(tokens, length, pos, T, count, out, span=0, ctx=None):

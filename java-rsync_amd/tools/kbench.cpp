@@ -178,12 +178,30 @@ static int tokens_main(int argc, char** argv) {
 //   * token_scan_kernel walking it, and walking a stream of 2^20 consecutive match tokens, each against a
 //     device-to-host copy of the same stream (the download a host walk needs), into pageable and into pinned memory.
 //   * token_scan_batch_kernel on one file at 1, 4, 8 and 16 waves to a round against token_scan_kernel, rep by rep;
+//   * the whole walk of both streams as the library drives it, tokens_wide = KBENCH_WIDE (default 8) against 0 and
+//     against the pinned download, on both walk kernels, in wall-clock time; token_run_kernel alone; and the cost of
+//     a finder launch that proves nothing (wide_walks);
 //   * KBENCH_UNTOKENS_FILES=<n>: the walk of a segment of n streams of config 4's shape (128 MiB files at
 //     B = 8192: half of them identical -- 16384 consecutive match tokens -- and half with every other block replaced
 //     -- a match token and an 8192-byte literal token in turn, 16384 records), as the library drives it:
 //     rsh_receiver_combine_batch_resident's rounds (one launch for all files at 4096 records each, one download of the
 //     TokScanOuts, one copy launch of the records) against rsh_receiver_combine_resident's per file (a launch at 65536
 //     records and two small downloads each), wall time.
+// KBENCH_WIDE_NOYIELD=K: the segment's and the half-modified stream's walks below launch the kernels' tokens_wide
+// instantiation with that K (their streams never yield: a pass that did would show as walk=MISMATCH), for the "no harm"
+// comparison against the same rows without it.
+static int32_t noyield_wide() { return getenv("KBENCH_WIDE_NOYIELD") ? atoi(getenv("KBENCH_WIDE_NOYIELD")) : 0; }
+static rsh::TokLong* noyield_lngs(size_t n) {
+    static rsh::TokLong* d = nullptr;
+    static size_t have = 0;
+    if (noyield_wide() <= 0) return nullptr;
+    if (n > have) {
+        CK(hipMalloc(&d, n * sizeof(rsh::TokLong)));
+        have = n;
+    }
+    return d;
+}
+
 static bool segment_walk(int nfiles, int reps, int32_t cyc, hipStream_t s) {
     const int64_t blocks = 16384, T = 8192;
     std::vector<uint8_t> ident((size_t)(4 * blocks + 4), 0), half;
@@ -241,7 +259,8 @@ static bool segment_walk(int nfiles, int reps, int32_t cyc, hipStream_t s) {
                 rounds = 0;
                 while (!cur.empty()) {
                     memcpy(live, cur.data(), cur.size() * sizeof(int32_t));
-                    CK(rsh::launch_token_scan_batch(jobs, live, (uint32_t)cur.size(), d_outs, cyc, s));
+                    CK(rsh::launch_token_scan_batch(jobs, live, (uint32_t)cur.size(), d_outs, cyc, s, noyield_wide(),
+                                                       noyield_lngs((size_t)nfiles)));
                     CK(hipMemcpyAsync(h_outs, d_outs, (size_t)nfiles * sizeof(rsh::TokScanOut), hipMemcpyDeviceToHost, s));
                     CK(hipStreamSynchronize(s));
                     uint32_t ne = 0;
@@ -272,7 +291,7 @@ static bool segment_walk(int nfiles, int reps, int32_t cyc, hipStream_t s) {
                     int64_t from = 0;
                     do {
                         CK(rsh::launch_token_scan(d_st[(size_t)f], lens[(size_t)f], from, reinterpret_cast<rsh::TokRun*>(d_runs1),
-                                                  cap1, d_out1, cyc, nullptr, s));
+                                                  cap1, d_out1, cyc, nullptr, s, noyield_wide(), noyield_lngs((size_t)nfiles)));
                         CK(hipMemcpyAsync(h_out1, d_out1, sizeof(rsh::TokScanOut), hipMemcpyDeviceToHost, s));
                         CK(hipStreamSynchronize(s));
                         if (h_out1->n > 0) {
@@ -332,8 +351,8 @@ static bool half_walk(int reps, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
         for (int k = 0; k < 4; ++k) {
             CK(hipStreamSynchronize(s));
             CK(hipEventRecord(e0, s));
-            if (k < 2) CK(rsh::launch_token_scan(st, len, 0, d_runs, cap, d_out, k == 0, nullptr, s));
-            else CK(rsh::launch_token_scan_batch(pj, plive, 1, d_out, k == 2, s));
+            if (k < 2) CK(rsh::launch_token_scan(st, len, 0, d_runs, cap, d_out, k == 0, nullptr, s, noyield_wide(), noyield_lngs(1)));
+            else CK(rsh::launch_token_scan_batch(pj, plive, 1, d_out, k == 2, s, noyield_wide(), noyield_lngs(1)));
             CK(hipEventRecord(e1, s));
             CK(hipEventSynchronize(e1));
             float ms;
@@ -352,6 +371,155 @@ static bool half_walk(int reps, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
         printf("  %s\n", ok ? "walk=ok" : "walk=MISMATCH");
     }
     return ok;
+}
+
+// Wide rounds (option tokens_wide; token_scan.h).  The whole walk of one stream as the library drives it -- every pass,
+// its head's download, the finder's launch for a pass that yielded and its word's download, each synchronisation -- in
+// wall-clock time, tokens_wide = K (KBENCH_WIDE, default 8) against 0 rep by rep, on token_scan_kernel (form 0) and on
+// token_scan_batch_kernel (form 1); beside it the stream's download into pinned memory, the same way.  Returns the
+// average ms of {K, 0, d2h}; *ok: the walk ended at the stream's end with `records` records.
+struct WideWalk {
+    rsh::TokRun* d_runs;
+    uint8_t *d_head, *h_head;  // TokScanOut, cycles, TokLong: 64 bytes (device; pinned)
+    rsh::TokScanJob* pj;
+    rsh::TokRunJob* prj;
+    int32_t* plive;
+};
+static bool wide_walk_once(const WideWalk& W, const uint8_t* st, int64_t len, int form, int32_t K, int32_t cyc, hipStream_t s,
+                           int64_t* finds, int64_t* passes, int64_t* records) {
+    int64_t from = 0;
+    *finds = *passes = *records = 0;
+    rsh::TokScanOut* d_out = reinterpret_cast<rsh::TokScanOut*>(W.d_head);
+    rsh::TokLong* d_lng = reinterpret_cast<rsh::TokLong*>(W.d_head + 32);
+    for (;;) {
+        if (form == 0) {
+            CK(rsh::launch_token_scan(st, len, from, W.d_runs, 1024, d_out, cyc, nullptr, s, K, d_lng));
+        } else {
+            *W.pj = rsh::TokScanJob{st, len, from, W.d_runs, 1024};
+            CK(rsh::launch_token_scan_batch(W.pj, W.plive, 1, d_out, cyc, s, K, d_lng));
+        }
+        CK(hipMemcpyAsync(W.h_head, W.d_head, K > 0 ? 64 : 32, hipMemcpyDeviceToHost, s));
+        CK(hipStreamSynchronize(s));
+        rsh::TokScanOut so;
+        memcpy(&so, W.h_head, sizeof(so));
+        ++*passes;
+        *records += so.n;
+        if (so.status == rsh::TOK_SCAN_END) return so.pos == len;
+        if (so.status == rsh::TOK_SCAN_MORE) {
+            from = so.pos;
+            continue;
+        }
+        if (so.status != rsh::TOK_SCAN_LONG) return false;
+        rsh::TokLong lng;
+        memcpy(&lng, W.h_head + 32, sizeof(lng));
+        int64_t m = 0;
+        if (rsh::tok_run_job(st, len, so.pos, lng.last, 0, W.prj)) {
+            const int64_t C = rsh::tok_run_chunk_tokens(W.prj->v);
+            CK(rsh::launch_token_run(W.prj, 1, rsh::tok_run_groups((W.prj->max + C - 1) / C, 0), d_lng, s));
+            CK(hipMemcpyAsync(W.h_head + 32, W.d_head + 32, 8, hipMemcpyDeviceToHost, s));
+            CK(hipStreamSynchronize(s));
+            uint64_t word;
+            memcpy(&word, W.h_head + 32, 8);
+            m = (int64_t)std::min<uint64_t>(word, (uint64_t)W.prj->max);
+            ++*finds;
+        }
+        from = so.pos + m * rsh::tok_run_stride(lng.last);
+    }
+}
+static bool wide_walks(const char* name, const uint8_t* st, int64_t len, int reps, int32_t cyc, hipStream_t s, uint8_t* pinned) {
+    const int32_t K = getenv("KBENCH_WIDE") ? atoi(getenv("KBENCH_WIDE")) : 8;
+    WideWalk W;
+    CK(hipMalloc(&W.d_runs, 1024 * sizeof(rsh::TokRun)));
+    CK(hipMalloc(&W.d_head, 64));
+    CK(hipHostMalloc(&W.h_head, 64, hipHostMallocDefault));
+    CK(hipHostMalloc(&W.pj, sizeof(rsh::TokScanJob), hipHostMallocDefault));
+    CK(hipHostMalloc(&W.prj, sizeof(rsh::TokRunJob), hipHostMallocDefault));
+    CK(hipHostMalloc(&W.plive, sizeof(int32_t), hipHostMallocDefault));
+    W.plive[0] = 0;
+    bool all = true;
+    for (int form = 0; form < 2; ++form) {
+        double t[3] = {0, 0, 0}, bt[3] = {1e30, 1e30, 1e30};
+        int64_t finds[2] = {0, 0}, passes[2] = {0, 0}, records[2] = {0, 0};
+        for (int r = 0; r < reps + 1; ++r) {
+            for (int k = 0; k < 3; ++k) {
+                CK(hipStreamSynchronize(s));
+                const auto a = std::chrono::steady_clock::now();
+                if (k < 2) {
+                    all = wide_walk_once(W, st, len, form, k == 0 ? K : 0, cyc, s, &finds[k], &passes[k], &records[k]) && all;
+                } else {
+                    CK(hipMemcpyAsync(pinned, st, (size_t)len, hipMemcpyDeviceToHost, s));
+                    CK(hipStreamSynchronize(s));
+                }
+                const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+                if (r == 0) continue;
+                t[k] += ms;
+                bt[k] = std::min(bt[k], ms);
+            }
+        }
+        all = all && records[0] == records[1];
+        printf("whole walk %-8s %s  tokens_wide=%d avg %.4f ms best %.4f ms (passes %lld, finder launches %lld)  tokens_wide=0 avg "
+               "%.4f ms best %.4f ms (passes %lld)  d2h pinned avg %.4f ms best %.4f ms  wide / plain %.3f  wide / d2h %.3f  %s\n",
+               name, form ? "four waves" : "one wave  ", K, t[0] / reps, bt[0], (long long)passes[0], (long long)finds[0],
+               t[1] / reps, bt[1], (long long)passes[1], t[2] / reps, bt[2], t[0] / t[1], t[0] / t[2], all ? "walk=ok" : "walk=MISMATCH");
+    }
+    // the finder alone over the whole run from the stream's first token (event time), and what a yield that proves
+    // nothing costs: the launch and its word's download from a position where the next token ends the run (wall clock)
+    {
+        rsh::TokScanOut so;
+        CK(rsh::launch_token_scan(st, len, 0, W.d_runs, 1024, reinterpret_cast<rsh::TokScanOut*>(W.d_head), cyc, nullptr, s, 1,
+                                  reinterpret_cast<rsh::TokLong*>(W.d_head + 32)));
+        CK(hipMemcpyAsync(W.h_head, W.d_head, 64, hipMemcpyDeviceToHost, s));
+        CK(hipStreamSynchronize(s));
+        memcpy(&so, W.h_head, sizeof(so));
+        rsh::TokLong lng;
+        memcpy(&lng, W.h_head + 32, sizeof(lng));
+        if (so.status == rsh::TOK_SCAN_LONG && rsh::tok_run_job(st, len, so.pos, lng.last, 0, W.prj)) {
+            const int64_t C = rsh::tok_run_chunk_tokens(W.prj->v);
+            const uint32_t G = rsh::tok_run_groups((W.prj->max + C - 1) / C, 0);
+            rsh::TokLong* d_lng = reinterpret_cast<rsh::TokLong*>(W.d_head + 32);
+            hipEvent_t e0, e1;
+            CK(hipEventCreate(&e0));
+            CK(hipEventCreate(&e1));
+            float tk = 0, bk = 1e30f;
+            double ty = 0, by = 1e30;
+            uint64_t word = 0;
+            for (int r = 0; r < reps + 1; ++r) {
+                CK(hipMemsetAsync(d_lng, 0xFF, 8, s));
+                CK(hipEventRecord(e0, s));
+                CK(rsh::launch_token_run(W.prj, 1, G, d_lng, s));
+                CK(hipEventRecord(e1, s));
+                CK(hipEventSynchronize(e1));
+                float ms;
+                CK(hipEventElapsedTime(&ms, e0, e1));
+                CK(hipMemcpy(&word, d_lng, 8, hipMemcpyDeviceToHost));
+                // a finder that proves nothing: asked for a run that the very next token does not continue
+                rsh::TokRunJob none = *W.prj;
+                none.v = none.v > 0 ? none.v + 1 : none.v - 1;
+                const rsh::TokRunJob keep = *W.prj;
+                *W.prj = none;
+                CK(hipMemsetAsync(d_lng, 0xFF, 8, s));
+                CK(hipStreamSynchronize(s));
+                const auto a = std::chrono::steady_clock::now();
+                CK(rsh::launch_token_run(W.prj, 1, G, d_lng, s));
+                CK(hipMemcpyAsync(W.h_head + 32, W.d_head + 32, 8, hipMemcpyDeviceToHost, s));
+                CK(hipStreamSynchronize(s));
+                const double y = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+                uint64_t w0;
+                memcpy(&w0, W.h_head + 32, 8);
+                all = all && w0 == 0;
+                *W.prj = keep;
+                if (r == 0) continue;
+                tk += ms;
+                bk = std::min(bk, ms);
+                ty += y;
+                by = std::min(by, y);
+            }
+            printf("token_run %-8s tokens=%lld groups=%u  kernel avg %.4f ms best %.4f ms  proved %llu  |  launch + download of a "
+                   "finder that proves nothing (wall clock): avg %.4f ms best %.4f ms\n",
+                   name, (long long)W.prj->max, G, tk / reps, bk, (unsigned long long)word, ty / reps, by);
+        }
+    }
+    return all;
 }
 
 static int untokens_main(int argc, char** argv) {
@@ -524,6 +692,8 @@ static int untokens_main(int argc, char** argv) {
                    ok ? "walk=ok" : "walk=MISMATCH");
         }
     }
+    walk_ok = wide_walks("literals", stream, slen, reps, kCyc, s, pinned) && walk_ok;
+    walk_ok = wide_walks("matches", mstream, mlen, reps, kCyc, s, pinned) && walk_ok;
     walk_ok = half_walk(reps, s, e0, e1) && walk_ok;
     if (getenv("KBENCH_UNTOKENS_FILES"))
         for (int32_t cyc : {1, 0}) walk_ok = segment_walk(atoi(getenv("KBENCH_UNTOKENS_FILES")), reps, cyc, s) && walk_ok;
