@@ -251,6 +251,46 @@ int rsh_debug_io_selftest(rsh_ctx* ctx, int32_t form, const rsh_io_op* ops, int3
 int rsh_debug_window_weak_selftest(rsh_ctx* ctx, const void* d_data, int64_t n, int32_t block_length, const int64_t* p,
                                    int32_t count, int32_t by_block, int32_t* out);
 
+/* The batched flush chain (resolver.h FlushChain; Sender.java:1294-1310) as HipBackend::first_hit runs it for
+ * flush_probe, through the production planner and launchers unchanged and with the job built as there: flush_positions,
+ * launch_window_weak and launch_gather_bytes into device memory, launch_flush_chain.  d_src[0, n): the source in device
+ * memory; flushes at f + 10 B i, i < K (1 .. 4096, f + 10 B (K - 1) + B <= n: what the resolver's flush_chain_at
+ * produces), the rolling value at f desynced by (el, eh); last: the last position the Sender's loop visits.  out[2 i],
+ * out[2 i + 1]: step i's desync.  iv_e: 2 K words -- words 2 i, 2 i + 1 the e_lo, e_hi the kernel wrote into interval i
+ * of the probe's list for i < niv (0 .. K), and the 0xA5A5A5A5 the entry put there before the launch for i >= niv. */
+int rsh_debug_flush_chain_selftest(rsh_ctx* ctx, const void* d_src, int64_t n, int32_t block_length, int64_t last,
+                                   int64_t f, int32_t K, uint32_t el, uint32_t eh, int32_t niv, uint32_t* out,
+                                   uint32_t* iv_e);
+/* Its host twin, without a device: flush_chain_host over the host source src[0, n), with the sums and bytes at
+ * flush_positions computed plainly.  out[2 i], out[2 i + 1] for the *n_steps steps the host form takes (it stops after
+ * the first step whose interval would start past `last`); *n_iv: the intervals among them. */
+int rsh_debug_flush_chain_host(const uint8_t* src, int64_t n, int32_t block_length, int64_t last, int64_t f, int32_t K,
+                               uint32_t el, uint32_t eh, uint32_t* out, int32_t* n_steps, int32_t* n_iv);
+
+/* One range probe of a single file as HipBackend::first_hit runs it, through the production planners and launchers
+ * unchanged and in its order: launch_table_clear and launch_table_insert of keys[0, nkeys) (small != 0: the keys go to
+ * ScanFile::small instead, 1 .. 8 of them), probe_plan per interval with seg_len (-1: probe_seg_len's own choice;
+ * 0: tiles only; else a multiple of 16384 up to 131072), probe_partials, the blocks' anchors T(k B) by
+ * launch_window_weak as head mode fills them, launch_probe_out_reset, launch_probe_first, launch_probe_long and
+ * launch_hit_window with the bucket kernel over table_weak[0, C) (host memory; uploaded).  ivs[0, niv): ascending,
+ * disjoint, 0 <= a < b <= n.  nwin 0 .. 4, next_sums 0 .. 3.  out: the raw record.  hit[0, hit_len), hit_len >= 16 +
+ * nwin * block_length: what ScanFile::hit holds afterwards, every byte 0xA5 before the launches (the caller's guard
+ * bytes past the windows included).  bucket: the HIT_BUCKET_INTS (2 + 256 + 64 * 4) ints, every byte 0xA5 before the
+ * launches.  plan (may be NULL): tiles, partial tiles, segments, the segment length taken. */
+typedef struct {
+    int64_t a, b, anchor;
+    uint32_t e_lo, e_hi;
+} rsh_probe_iv;
+typedef struct {
+    uint64_t first, count;
+    uint64_t pos[64];
+    uint32_t key[64];
+} rsh_probe_out;
+int rsh_debug_probe_selftest(rsh_ctx* ctx, const void* d_src, int64_t n, int32_t block_length, const int32_t* keys,
+                             int32_t nkeys, int32_t small, const rsh_probe_iv* ivs, int32_t niv, int64_t seg_len,
+                             int32_t nwin, int32_t next_sums, const int32_t* table_weak, int32_t C, rsh_probe_out* out,
+                             uint8_t* hit, int64_t hit_len, int32_t* bucket, int64_t plan[4]);
+
 /* The phase map of a single-file scan (option scan_phase_map = k > 0: once k phase-shifted speculations have gone out,
  * the next hint that nothing covers maps the rest of the source; 0, the default: never).  A sample at position a keys
  * the positions [a, a + 2 B) whose window is full and looks them up in the table; its anchor is the smallest p in

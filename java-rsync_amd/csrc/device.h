@@ -299,6 +299,8 @@ void probe_tiles(int64_t a, int64_t b, int64_t B, int32_t iv, std::vector<ProbeT
 int64_t probe_seg_len(int64_t full_positions, int64_t B);
 int64_t probe_full_positions(int64_t a, int64_t b, int64_t n, int64_t B);
 // As probe_tiles, with the full-window part of a long interval as segments of seg_len positions (host side).
+// Where tiles follow the segments (the interval reaches the shrinking windows), they start at a tile start at or
+// before the last full window: no position is probed by both.
 void probe_plan(int64_t a, int64_t b, int64_t n, int64_t B, int32_t iv, int64_t seg_len, std::vector<ProbeTile>* tiles,
                 std::vector<ProbeSeg>* segs);
 // The segments' launch (writes the same ProbeOut records as the tiles' launch; either order).

@@ -442,9 +442,15 @@ void probe_plan(int64_t a, int64_t b, int64_t n, int64_t B, int32_t iv, int64_t 
         probe_tiles(a, b, B, iv, tiles);
         return;
     }
-    for (int64_t q = a & ~(int64_t)15; q < full_end; q += seg_len)
-        segs->push_back(ProbeSeg{q, iv, (int32_t)(full_end - q < seg_len ? full_end - q : seg_len)});
-    probe_tiles(full_end, b, B, iv, tiles);  // the shrinking windows near the end, if the interval reaches them
+    // Where tiles follow (the shrinking windows near the end, if the interval reaches them), they take over at a tile
+    // start: tiles lie in block coordinates and probe_first_kernel reports every position of a tile that lies in the
+    // interval, so a tile that began inside the segments' part would list the hits between its start and full_end a
+    // second time (ProbeOut::pos must be distinct: hit_window_kernel ranks the listed positions, window_slots sorts them).
+    int64_t cut = full_end;
+    if (b > full_end) cut = full_end / B * B + (full_end % B) / PROBE_TILE * PROBE_TILE;
+    for (int64_t q = a & ~(int64_t)15; q < cut; q += seg_len)
+        segs->push_back(ProbeSeg{q, iv, (int32_t)(cut - q < seg_len ? cut - q : seg_len)});
+    probe_tiles(cut, b, B, iv, tiles);
 }
 
 // Pass-free probe over long segments (see ProbeSeg): T(q0) digested by the workgroup once, then sub-segments of

@@ -809,3 +809,227 @@ int emit_events(rsh_ctx* c, rsh::ResolveResult& r, rsh_event* ev, int64_t cap, i
 }
 
 }  // namespace rshi
+
+// ---- rsync_hip_debug.h: the flush chain and one range probe as HipBackend::first_hit runs them (the desync lattice,
+// tests/test_gpu_desync_lattice.py); the production planners and launchers unchanged, no kernel of the entries' own ----
+#include "rsync_hip_debug.h"
+
+namespace {
+bool chain_args_ok(int64_t n, int32_t B, int64_t last, int64_t f, int32_t K) {
+    return n >= 1 && B >= 1 && B <= kMaxBlockLength && K >= 1 && K <= 4096 && f >= 0 && last >= 0 && last < n &&
+           f + 10 * (int64_t)B * (K - 1) + B <= n;
+}
+}  // namespace
+
+extern "C" int rsh_debug_flush_chain_host(const uint8_t* src, int64_t n, int32_t block_length, int64_t last, int64_t f,
+                                          int32_t K, uint32_t el, uint32_t eh, uint32_t* out, int32_t* n_steps,
+                                          int32_t* n_iv) {
+    if (!src || !out || !chain_args_ok(n, block_length, last, f, K)) return RSH_E_INVAL;
+    rsh::FlushChain q;
+    q.f = f, q.K = K, q.B = block_length, q.n = n, q.last = last, q.el = el, q.eh = eh;
+    std::vector<int64_t> tpos, bpos;
+    rsh::flush_positions(q, &tpos, &bpos);
+    std::vector<int32_t> tv(tpos.size());
+    std::vector<uint8_t> bv(bpos.size());
+    for (size_t i = 0; i < tpos.size(); ++i) {  // Rolling.compute over the window at tpos[i]
+        const int64_t p = tpos[i], w = std::min<int64_t>(q.B, n - p);
+        uint32_t s1 = 0, s2 = 0;
+        for (int64_t j = 0; j < w; ++j) {
+            s1 += (uint32_t)(int32_t)(int8_t)src[p + j];
+            s2 += s1;
+        }
+        tv[i] = (int32_t)((s1 & 0xFFFFu) | (s2 << 16));
+    }
+    for (size_t i = 0; i < bpos.size(); ++i) bv[i] = src[bpos[i]];
+    std::vector<rsh::FlushStep> steps;
+    std::vector<rsh::ProbeInterval> ivs;
+    rsh::flush_chain_host(q, tv.data(), bv.data(), &steps, &ivs);
+    for (size_t i = 0; i < steps.size(); ++i) {
+        out[2 * i] = steps[i].elo;
+        out[2 * i + 1] = steps[i].ehi;
+    }
+    if (n_steps) *n_steps = (int32_t)steps.size();
+    if (n_iv) *n_iv = (int32_t)ivs.size();
+    return RSH_OK;
+}
+
+extern "C" int rsh_debug_flush_chain_selftest(rsh_ctx* ctx, const void* d_src, int64_t n, int32_t block_length,
+                                              int64_t last, int64_t f, int32_t K, uint32_t el, uint32_t eh, int32_t niv,
+                                              uint32_t* out, uint32_t* iv_e) {
+    if (!ctx || !d_src || !out || !iv_e || !chain_args_ok(n, block_length, last, f, K) || niv < 0 || niv > K)
+        return RSH_E_INVAL;
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    rsh::FlushChain q;
+    q.f = f, q.K = K, q.B = block_length, q.n = n, q.last = last, q.el = el, q.eh = eh;
+    std::vector<int64_t> tpos, bpos;
+    rsh::flush_positions(q, &tpos, &bpos);
+    const int64_t nt = (int64_t)tpos.size(), nb = (int64_t)bpos.size();
+    RSH_HIP(ctx->h_files.ensure(sizeof(rsh::ScanFile)));
+    RSH_HIP(ctx->h_iv.ensure((size_t)(K + 1) * sizeof(rsh::ProbeIv)));
+    RSH_HIP(ctx->h_fgw.ensure((size_t)(nt + nb) * sizeof(rsh::GatherEnt)));
+    RSH_HIP(ctx->h_fjobs.ensure(sizeof(rsh::FlushChainJob)));
+    RSH_HIP(ctx->h_fout.ensure((size_t)(2 * K) * sizeof(uint32_t)));
+    RSH_HIP(ctx->fc_dev.ensure((size_t)(nt * 4 + nb + 16)));
+    rsh::ScanFile* F = ctx->h_files.as<rsh::ScanFile>();
+    memset(F, 0, sizeof(rsh::ScanFile));
+    F->data = static_cast<const uint8_t*>(d_src);
+    F->n = n;
+    F->B = (uint32_t)block_length;
+    rsh::ProbeIv* hiv = ctx->h_iv.as<rsh::ProbeIv>();
+    memset(hiv, 0xA5, (size_t)K * sizeof(rsh::ProbeIv));
+    uint32_t* hfo = ctx->h_fout.as<uint32_t>();
+    memset(hfo, 0xA5, (size_t)(2 * K) * sizeof(uint32_t));
+    // (from here on as HipBackend::first_hit with fc_ set, scan_backend.h)
+    rsh::GatherEnt* hfg = ctx->h_fgw.as<rsh::GatherEnt>();
+    rsh::FlushChainJob* hj = ctx->h_fjobs.as<rsh::FlushChainJob>();
+    for (int64_t i = 0; i < nt; ++i) hfg[i] = rsh::GatherEnt{tpos[(size_t)i], 0, 0};
+    for (int64_t i = 0; i < nb; ++i) hfg[nt + i] = rsh::GatherEnt{bpos[(size_t)i], 0, 0};
+    int32_t* d_tv = ctx->fc_dev.as<int32_t>();
+    uint8_t* d_bv = reinterpret_cast<uint8_t*>(d_tv + nt);
+    RSH_HIP(rsh::launch_window_weak(F, hfg, (uint32_t)nt, d_tv, ctx->stream));
+    RSH_HIP(rsh::launch_gather_bytes(F, hfg + nt, (uint32_t)nb, d_bv, ctx->stream));
+    *hj = rsh::FlushChainJob{d_tv, d_bv, hiv, hfo, q.f, q.B, q.n, q.last, (int32_t)q.K, niv, q.el, q.eh};
+    RSH_HIP(rsh::launch_flush_chain(hj, 1, ctx->stream));
+    RSH_HIP(hipStreamSynchronize(ctx->stream));
+    memcpy(out, hfo, (size_t)(2 * K) * sizeof(uint32_t));
+    for (int32_t i = 0; i < K; ++i) {
+        iv_e[2 * i] = hiv[i].e_lo;
+        iv_e[2 * i + 1] = hiv[i].e_hi;
+    }
+    return RSH_OK;
+}
+
+extern "C" int rsh_debug_probe_selftest(rsh_ctx* ctx, const void* d_src, int64_t n, int32_t block_length,
+                                        const int32_t* keys, int32_t nkeys, int32_t small, const rsh_probe_iv* ivs,
+                                        int32_t niv, int64_t seg_len, int32_t nwin, int32_t next_sums,
+                                        const int32_t* table_weak, int32_t C, rsh_probe_out* out, uint8_t* hit,
+                                        int64_t hit_len, int32_t* bucket, int64_t plan[4]) {
+    static_assert(sizeof(rsh_probe_out) == sizeof(rsh::ProbeOut) && offsetof(rsh_probe_out, key) == offsetof(rsh::ProbeOut, key),
+                  "rsh_probe_out is ProbeOut");
+    static_assert(sizeof(rsh_probe_iv) == sizeof(rsh::ProbeInterval), "rsh_probe_iv is ProbeInterval");
+    const int64_t B = block_length;
+    if (!ctx || !d_src || !ivs || !out || !hit || !bucket || n < 1 || B < 1 || B > kMaxBlockLength || B > n || niv < 1 ||
+        nkeys < 0 || (nkeys > 0 && !keys) || (small && (nkeys < 1 || nkeys > rsh::PROBE_SMALL_KEYS)) || nwin < 0 ||
+        nwin > rsh::HIT_WINDOWS || next_sums < 0 || next_sums > rsh::NEXT_SUMS_MAX || C < 0 || (C > 0 && !table_weak) ||
+        hit_len < 16 + nwin * B)
+        return RSH_E_INVAL;
+    if (seg_len < -1 || (seg_len > 0 && (seg_len % rsh::PROBE_LONG_SUB != 0 ||
+                                         seg_len > rsh::PROBE_LONG_PASSES * rsh::PROBE_LONG_SUB)))
+        return RSH_E_INVAL;
+    for (int32_t i = 0; i < niv; ++i)
+        if (ivs[i].a < 0 || ivs[i].a >= ivs[i].b || ivs[i].b > n || ivs[i].anchor < 0 || ivs[i].anchor > n ||
+            (i > 0 && ivs[i].a < ivs[i - 1].b))
+            return RSH_E_INVAL;
+    RSH_CLAIM(ctx);
+    RSH_HIP(hipSetDevice(ctx->device));
+    rsh_ctx* c_ = ctx;
+    hipStream_t rs_ = ctx->stream;
+    const int64_t count = niv, n_ = n, B_ = B, na = (n + B - 1) / B;
+    // the key set: a probe hash of its own, as first_hit's `keys` (or ScanFile::small, as the batched rounds')
+    const uint32_t ns = pow2_at_least(2 * (uint64_t)nkeys + 2);
+    RSH_HIP(c_->dslots.ensure(ns * sizeof(unsigned long long)));
+    RSH_HIP(c_->h_keys.ensure((size_t)(nkeys + 1) * sizeof(int32_t)));
+    int32_t* hk = c_->h_keys.as<int32_t>();
+    if (nkeys > 0) memcpy(hk, keys, (size_t)nkeys * sizeof(int32_t));
+    RSH_HIP(rsh::launch_table_clear(c_->dslots.as<unsigned long long>(), ns, rs_));
+    if (!small) RSH_HIP(rsh::launch_table_insert(c_->dslots.as<unsigned long long>(), ns - 1, hk, (uint32_t)nkeys, rs_));
+    std::vector<rsh::ProbeTile> tiles_;
+    std::vector<rsh::ProbeSeg> segs_;
+    std::vector<rsh::PartialTile> ptiles_;
+    int64_t full = 0;
+    for (int64_t i = 0; i < count; ++i) full += rsh::probe_full_positions(ivs[i].a, ivs[i].b, n_, B_);
+    if (seg_len < 0) seg_len = rsh::probe_seg_len(full, B_);
+    for (int64_t i = 0; i < count; ++i) rsh::probe_plan(ivs[i].a, ivs[i].b, n_, B_, (int32_t)i, seg_len, &tiles_, &segs_);
+    rsh::probe_partials(&tiles_, 0, B_, 0, &ptiles_);
+    if (plan) {
+        plan[0] = (int64_t)tiles_.size();
+        plan[1] = (int64_t)ptiles_.size();
+        plan[2] = (int64_t)segs_.size();
+        plan[3] = seg_len;
+    }
+    RSH_HIP(c_->h_iv.ensure((size_t)(count + 1) * sizeof(rsh::ProbeIv)));
+    RSH_HIP(c_->h_tiles.ensure((tiles_.size() + 1) * sizeof(rsh::ProbeTile)));
+    RSH_HIP(c_->h_ptiles.ensure((ptiles_.size() + 1) * sizeof(rsh::PartialTile)));
+    RSH_HIP(c_->h_psegs.ensure((segs_.size() + 1) * sizeof(rsh::ProbeSeg)));
+    RSH_HIP(c_->h_first.ensure(2 * sizeof(rsh::ProbeOut)));
+    RSH_HIP(c_->h_hit.ensure((size_t)hit_len));
+    RSH_HIP(c_->h_bucket.ensure((rsh::HIT_BUCKET_INTS + 1) * sizeof(int32_t)));
+    RSH_HIP(c_->h_files.ensure(sizeof(rsh::ScanFile)));
+    RSH_HIP(c_->h_pos.ensure((size_t)na * sizeof(rsh::GatherEnt)));
+    RSH_HIP(c_->partials.ensure((ptiles_.size() + 1) * sizeof(int4)));
+    RSH_HIP(c_->bucket.ensure(rsh::HIT_BUCKET_INTS * sizeof(int32_t)));
+    RSH_HIP(c_->first.ensure(kFirstSlots * sizeof(rsh::ProbeOut)));
+    RSH_HIP(c_->haw.ensure((size_t)na * 4));
+    RSH_HIP(c_->weak.ensure((size_t)C * 4 + 4));
+    rsh::ProbeIv* hiv = c_->h_iv.as<rsh::ProbeIv>();
+    rsh::ProbeTile* ht = c_->h_tiles.as<rsh::ProbeTile>();
+    rsh::PartialTile* hpt = c_->h_ptiles.as<rsh::PartialTile>();
+    rsh::ProbeSeg* hsg = c_->h_psegs.as<rsh::ProbeSeg>();
+    rsh::ProbeOut* hf = c_->h_first.as<rsh::ProbeOut>();
+    uint8_t* hh = c_->h_hit.as<uint8_t>();
+    int32_t* hb = c_->h_bucket.as<int32_t>();
+    memset(hh, 0xA5, (size_t)hit_len);
+    RSH_HIP(hipMemsetAsync(c_->bucket.p, 0xA5, rsh::HIT_BUCKET_INTS * sizeof(int32_t), rs_));
+    if (C > 0) RSH_HIP(hipMemcpyAsync(c_->weak.p, table_weak, (size_t)C * 4, hipMemcpyHostToDevice, rs_));
+    if (c_->first_used % kFirstSlots == 0)
+        RSH_HIP(rsh::launch_probe_out_reset(c_->first.as<rsh::ProbeOut>(), (uint32_t)kFirstSlots, rs_));
+    rsh::ProbeOut* d_first = c_->first.as<rsh::ProbeOut>() + c_->first_used++ % kFirstSlots;
+    for (int64_t i = 0; i < count; ++i)
+        hiv[i] = rsh::ProbeIv{ivs[i].a, ivs[i].b, ivs[i].anchor, ivs[i].e_lo & 0xFFFFu, ivs[i].e_hi & 0xFFFFu, 0, 0};
+    if (!tiles_.empty()) memcpy(ht, tiles_.data(), tiles_.size() * sizeof(rsh::ProbeTile));
+    if (!ptiles_.empty()) memcpy(hpt, ptiles_.data(), ptiles_.size() * sizeof(rsh::PartialTile));
+    if (!segs_.empty()) memcpy(hsg, segs_.data(), segs_.size() * sizeof(rsh::ProbeSeg));
+    rsh::ScanFile* F = c_->h_files.as<rsh::ScanFile>();
+    memset(F, 0, sizeof(rsh::ScanFile));
+    F->data = static_cast<const uint8_t*>(d_src);
+    F->n = n_;
+    F->B = (uint32_t)B_;
+    F->table_weak = c_->weak.as<int32_t>();
+    F->C = C;
+    F->nsmall = 0;
+    if (small) {
+        F->nsmall = nkeys;
+        for (int32_t j = 0; j < nkeys; ++j) F->small[j] = (uint32_t)keys[j];
+    }
+    F->aligned_weak = c_->haw.as<int32_t>();
+    F->slots = c_->dslots.as<unsigned long long>();
+    F->mask = ns - 1;
+    F->out = d_first;
+    F->iv0 = 0;
+    F->niv = (int32_t)count;
+    F->bucket = c_->bucket.as<int32_t>();
+    F->hit = hh;
+    F->nwin = nwin;
+    F->next_sums = next_sums;
+    {  // anchors T(kB) for the blocks these tiles sit in (head mode)
+        std::vector<uint8_t> ready((size_t)na, 0);
+        rsh::GatherEnt* hp = c_->h_pos.as<rsh::GatherEnt>();
+        uint32_t nanch = 0;
+        for (const rsh::ProbeTile& t : tiles_) {
+            const int64_t k = t.q0 / B_;
+            if (!ready[(size_t)k]) {
+                ready[(size_t)k] = 1;
+                hp[nanch++] = rsh::GatherEnt{k * B_, 0, 1};
+            }
+        }
+        if (nanch > 0) RSH_HIP(rsh::launch_window_weak(F, hp, nanch, nullptr, rs_));
+    }
+    rsh::ProbeArgs A;
+    A.files = F;
+    A.ivs = hiv;
+    A.tiles = ht;
+    A.partials = c_->partials.as<int4>();
+    RSH_HIP(rsh::launch_probe_first(A, (uint32_t)tiles_.size(), hpt, (uint32_t)ptiles_.size(), rs_));
+    RSH_HIP(rsh::launch_probe_long(A, hsg, (uint32_t)segs_.size(), rs_));
+    int32_t* req = hb + rsh::HIT_BUCKET_INTS;
+    *req = 0;
+    RSH_HIP(rsh::launch_hit_window(F, hiv, req, 1, C, rs_));
+    RSH_HIP(hipMemcpyAsync(hf, d_first, sizeof(rsh::ProbeOut), hipMemcpyDeviceToHost, rs_));
+    RSH_HIP(hipMemcpyAsync(hb, c_->bucket.p, rsh::HIT_BUCKET_INTS * sizeof(int32_t), hipMemcpyDeviceToHost, rs_));
+    RSH_HIP(hipStreamSynchronize(rs_));
+    memcpy(out, hf, sizeof(rsh::ProbeOut));
+    memcpy(hit, hh, (size_t)hit_len);
+    memcpy(bucket, hb, rsh::HIT_BUCKET_INTS * sizeof(int32_t));
+    return RSH_OK;
+}

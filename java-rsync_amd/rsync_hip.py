@@ -242,7 +242,8 @@ DEBUG_EXPORTS = ["rsh_debug_set_option", "rsh_debug_get_option", "rsh_debug_rese
                  "rsh_debug_k1_plan_batch", "rsh_debug_md5_device_selftest", "rsh_debug_md5_closing",
                  "rsh_debug_md5_plan", "rsh_debug_io_selftest", "rsh_debug_window_weak_selftest",
                  "rsh_debug_tokens_scan_rounds_selftest", "rsh_debug_tokens_run_selftest",
-                 "rsh_debug_tokens_run_extent", "rsh_debug_tokens_walk_selftest", "rsh_debug_walk_stats"]
+                 "rsh_debug_tokens_run_extent", "rsh_debug_tokens_walk_selftest", "rsh_debug_walk_stats",
+                 "rsh_debug_flush_chain_selftest", "rsh_debug_flush_chain_host", "rsh_debug_probe_selftest"]
 
 _LIB = None
 
@@ -392,6 +393,12 @@ def lib():
         "rsh_debug_md5_closing": ([P, I32, I64, P, ctypes.POINTER(I32)], ctypes.c_int),
         "rsh_debug_io_selftest": ([P, I32, P, I32, I64], ctypes.c_int),
         "rsh_debug_window_weak_selftest": ([P, P, I64, I32, P, I32, I32, P], ctypes.c_int),
+        "rsh_debug_flush_chain_selftest": ([P, P, I64, I32, I64, I64, I32, ctypes.c_uint32, ctypes.c_uint32, I32, P, P],
+                                           ctypes.c_int),
+        "rsh_debug_flush_chain_host": ([P, I64, I32, I64, I64, I32, ctypes.c_uint32, ctypes.c_uint32, P,
+                                        ctypes.POINTER(I32), ctypes.POINTER(I32)], ctypes.c_int),
+        "rsh_debug_probe_selftest": ([P, P, I64, I32, P, I32, I32, P, I32, I64, I32, I32, P, I32, P, P, I64, P, P],
+                                     ctypes.c_int),
         "rsh_debug_md5_plan": ([P, P, I32, I64, I64, I64, P, ctypes.POINTER(I32), P, ctypes.POINTER(I64),
                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], ctypes.c_int),
     }
@@ -684,6 +691,55 @@ def window_weak_selftest(ctx, d_data, n, block_length, positions, by_block=False
     _check(lib().rsh_debug_window_weak_selftest(ctx.handle, _addr(d_data), n, block_length, _ptr(p) if p.size else None,
                                                 p.size, int(bool(by_block)), _ptr(res)))
     return res if by_block else res[:p.size]
+
+
+def flush_chain_selftest(ctx, d_src, n, block_length, last, f, K, el, eh, niv=None):
+    """rsh_debug_flush_chain_selftest: flush_chain_kernel through its production gathers and launcher over the source
+    d_src[0, n) in device memory, flushes at f + 10 B i (i < K), the rolling value at f desynced by (el, eh).
+    -> (out, iv_e): uint32 arrays of shape (K, 2), step i's (elo, ehi) and what interval i of the probe's list holds
+    afterwards (0xA5A5A5A5 twice for i >= niv; niv None: K)."""
+    out, iv_e = np.zeros((K, 2), np.uint32), np.zeros((K, 2), np.uint32)
+    _check(lib().rsh_debug_flush_chain_selftest(ctx.handle, _addr(d_src), n, block_length, last, f, K, el, eh,
+                                                K if niv is None else niv, _ptr(out), _ptr(iv_e)))
+    return out, iv_e
+
+
+def flush_chain_host(src, block_length, last, f, K, el, eh):
+    """rsh_debug_flush_chain_host: flush_chain_host (resolver.cpp) over the host source, no device.
+    -> (out, n_iv): the (elo, ehi) of the steps the host form takes, shape (steps, 2), and its interval count."""
+    a = _u8(src)
+    out = np.zeros((K, 2), np.uint32)
+    ns, ni = ctypes.c_int32(), ctypes.c_int32()
+    _check(lib().rsh_debug_flush_chain_host(_ptr(a), a.size, block_length, last, f, K, el, eh, _ptr(out),
+                                            ctypes.byref(ns), ctypes.byref(ni)))
+    return out[:ns.value], ni.value
+
+
+PROBE_IV_DTYPE = np.dtype([("a", "<i8"), ("b", "<i8"), ("anchor", "<i8"), ("e_lo", "<u4"), ("e_hi", "<u4")])  # rsh_probe_iv
+PROBE_OUT_DTYPE = np.dtype([("first", "<u8"), ("count", "<u8"), ("pos", "<u8", 64), ("key", "<u4", 64)])  # rsh_probe_out
+HIT_BUCKET_INTS = 2 + 256 + 64 * 4
+
+
+def probe_selftest(ctx, d_src, n, block_length, keys, ivs, small=False, seg_len=0, nwin=1, next_sums=0,
+                   table_weak=(), guard=64):
+    """rsh_debug_probe_selftest: one range probe of the file d_src[0, n) as the single-file scan's backend runs it.
+    keys: the probe's key set (int32); ivs = [(a, b, anchor, e_lo, e_hi)], ascending and disjoint; seg_len -1:
+    probe_seg_len's choice, 0: tiles only; table_weak: the table hit_bucket_kernel searches.
+    -> (record, hit, bucket, plan): the ProbeOut as a PROBE_OUT_DTYPE scalar, the hit buffer (16 + nwin B + guard bytes,
+    0xA5 before the launches), the HIT_BUCKET_INTS ints (0xA5 bytes before the launches), (tiles, partial tiles,
+    segments, segment length)."""
+    k = np.ascontiguousarray(keys, dtype=np.int32)
+    iv = np.array([tuple(int(v) for v in x) for x in ivs], dtype=PROBE_IV_DTYPE)
+    tw = np.ascontiguousarray(table_weak, dtype=np.int32)
+    rec = np.zeros(1, PROBE_OUT_DTYPE)
+    hit = np.zeros(16 + nwin * block_length + guard, np.uint8)
+    bucket = np.zeros(HIT_BUCKET_INTS, np.int32)
+    plan = np.zeros(4, np.int64)
+    _check(lib().rsh_debug_probe_selftest(ctx.handle, _addr(d_src), n, block_length, _ptr(k) if k.size else None, k.size,
+                                          int(bool(small)), _ptr(iv), iv.size, seg_len, nwin, next_sums,
+                                          _ptr(tw) if tw.size else None, tw.size, _ptr(rec), _ptr(hit), hit.size,
+                                          _ptr(bucket), _ptr(plan)))
+    return rec[0], hit, bucket, tuple(int(v) for v in plan)
 
 
 def md5_device_selftest(jobs, slice_bytes=0, stop_after=-1, ctx=None):
